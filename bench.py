@@ -6,14 +6,21 @@ HeatmapGenerator at layer j=7 (conv3 block, d=64) with K=4 subspaces, U = ortho_
 the whole hot path: forward, LRP backward with the K+1 relevance clones, split/sum/sort
 (HeatmapGenerator.info semantics), inputs resident in HBM, outputs left in HBM.
 
-  python bench.py [--gpus N --steps K --warmup W --batch B]
+  python bench.py [--gpus N --steps K --warmup W --batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step` = wall time of the timed steps / K), nothing else.  --dump-outputs DIR also writes
+what the last timed step returned as DIR/<name>.npy (the inputs are seeded, so two builds can be
+compared output for output).  Everything below "Also reported" and every secondary leg runs
+only with --full.
+
   (N>1: either under torchrun --nproc-per-node N, or bench.py spawns the N ranks itself
    (drsa_audio_amd/utils/launch.py) before any GPU call; each rank explains its own batch, no
    collective on the data path -> weak scaling; time = max over ranks.  The N>1 run adds the
-   row-sharded DRSA leg (one RCCL all-reduce per step); every run has the task-parallel DRSA
-   grid leg (the reference's 90 independent problems spread over the ranks, strong scaling).)
+   row-sharded DRSA leg (one RCCL all-reduce per step); every --full run has the task-parallel
+   DRSA grid leg (the reference's 90 independent problems spread over the ranks, strong scaling).)
 
-Also reported: per-kernel HIP-event timings of the dominant kernel (roofline), the standard
+Also reported (--full): per-kernel HIP-event timings of the dominant kernel (roofline), the standard
 LRP rate at bs=64 (C2), the DRSA step rate at C3 (N=20000, d=64, K=4) with its objective
 checked against the CPU oracle, and the CPU baseline (oracle's zennit-structured restatement,
 K+1 batch replication like explainer.py:92) on a bounded sample.
@@ -620,6 +627,27 @@ def drsa_grid_bench(device, world, rank, steps=100, N=20000, classes=None):
                                         max(v["objective"] for v in res.values())]}
 
 
+# --------------------------------------------------------------------------- --dump-outputs
+DUMP_BUDGET_BYTES = 60_000_000     # all files of one dump together stay under 64 MB
+DUMP_SEED = 0
+
+
+def dump_outputs(path, out):
+    """Write the arrays one hot-path step returned (`out`: name -> device tensor, batch first) as
+    path/<name>.npy: floating tensors as float32, integer ones (the mask) as float64.  When the
+    whole batch exceeds DUMP_BUDGET_BYTES, the same seeded sample of batch rows (ascending, a
+    function of DUMP_SEED and the batch size alone) is taken from every array."""
+    os.makedirs(path, exist_ok=True)
+    B = next(iter(out.values())).size(0)
+    row_bytes = sum(v[0].numel() * (4 if v.is_floating_point() else 8) for v in out.values())
+    n = min(B, max(1, DUMP_BUDGET_BYTES // row_bytes))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False)) if n < B else np.arange(B)
+    for name, v in out.items():
+        a = v.index_select(0, torch.from_numpy(rows).to(v.device)).cpu()
+        np.save(os.path.join(path, name + ".npy"), (a.float() if a.is_floating_point() else a.double()).numpy())
+    log(f"[bench] wrote {len(out)} arrays, {n} of {B} batch rows, to {path}")
+
+
 # --------------------------------------------------------------------------- main
 LEGS = ("c2", "drsa", "frontend", "joint", "vggish", "sharded", "pipeline", "grid", "to_host", "clone")
 
@@ -638,10 +666,19 @@ def main():
     ap.add_argument("--grid-classes", type=int, default=10, help="classes of the DRSA grid (10 = the reference's)")
     ap.add_argument("--pipeline-samples", type=int, default=1000, help="samples per rank of the rank-local C4 leg")
     ap.add_argument("--pipeline-steps", type=int, default=100, help="DRSA steps of the rank-local C4 leg")
-    ap.add_argument("--legs", default="all",
-                    help="secondary legs to run: all, none, or a comma list of " + ",".join(LEGS))
+    ap.add_argument("--legs", default=None,
+                    help="with --full: secondary legs to run: all (default), none, or a comma list of " + ",".join(LEGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the per-kernel traced steps (roofline), the secondary legs "
+                         "and the CPU baselines, and add them to the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (HeatmapGenerator.info_device) as DIR/<name>.npy")
     args = ap.parse_args()
-    legs = set(LEGS) if args.legs == "all" else set() if args.legs == "none" else set(args.legs.split(","))
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.tag_order or args.legs not in (None, "none")):
+        ap.error("--tag-order and --legs need --full (a plain run times the headline only)")
+    legs = set(LEGS) if args.legs in (None, "all") else set() if args.legs == "none" else set(args.legs.split(","))
     if not legs <= set(LEGS):
         ap.error(f"--legs: unknown {sorted(legs - set(LEGS))}")
     if args.no_drsa:
@@ -661,7 +698,6 @@ def main():
 
     from drsa_audio_amd.utils.constants import LRP_NAME_MAP_GTZAN
     from drsa_audio_amd.xai.explain.explainer import HeatmapGenerator
-    from drsa_audio_amd.engine import get_engine
 
     B, K = args.batch, 4
     model = gtzan128().to(device)
@@ -700,6 +736,58 @@ def main():
         dt = max(t.tolist())
     ms = dt / args.steps * 1e3
     value = world * B * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hg.info_device)
+
+    out = {
+        "metric": "explained samples/sec (LRP+DRSA k=4)",
+        "value": value,
+        "unit": "explained samples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms,
+        "rank_ms_per_step": rank_ms,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": "synthetic (seeded log-mel-like 128x128 batches; random-init GTZAN-128 weights, "
+                "torch.manual_seed(0); U = ortho_group.rvs(64) seed 42)",
+        "config": {"workload": "GTZAN-128 HeatmapGenerator: LRP (WSquare/Gamma/Epsilon name map) + DRSA "
+                               "subspace heatmaps, K=4 at layer j=7 (conv3 block, d=64), sorted info dict",
+                   "standard_heatmap": "sum of the K concept heatmaps (standard='sum'; exact reformulation, "
+                                       "bit-exact vs the oracle); with --full, the reference's clone-0 form: "
+                                       "secondary.clone_mode; with the numpy info D2H: secondary.to_host",
+                   "global_batch": B * world, "per_gpu_batch": B, "input": "128x128 log-mel",
+                   "parallelism": f"data-parallel x{world} (no collective on the data path)",
+                   "launch": ("torchrun" if os.environ.get("TORCHELASTIC_RUN_ID") else
+                              "bench.py --gpus (own launcher)" if world > 1 else "single process"),
+                   "one_device_rehearsal": one_dev, "backend": backend if world > 1 else None},
+    }
+    if args.full:
+        log(f"[bench] headline {value:.0f} explained samples/s ({ms:.3f} ms/step); secondaries next")
+        extra = full_report(args, legs, world, rank, device, model, hg, x, value)
+        if rank == 0:
+            out.update(extra)
+    elif world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+
+
+def full_report(args, legs, world, rank, device, model, hg, x, value):
+    """--full: what the benchmark measures beside its headline, each in runs of its own after the
+    timed steps: per-kernel HIP-event times of traced steps (roofline, whole-path FLOP), the
+    secondary legs (--legs) and the CPU baselines.  Returns the fields these add to the result
+    line (rank 0; the other ranks leave the process group before the CPU baselines, and get None)."""
+    from drsa_audio_amd.utils.constants import LRP_NAME_MAP_GTZAN
+    from drsa_audio_amd.xai.explain.explainer import HeatmapGenerator
+    from drsa_audio_amd.engine import get_engine
+    if world > 1:
+        import torch.distributed as dist
+    B, K = args.batch, 4
 
     # ---- per-kernel timing (HIP events on the launch stream), separate traced steps ----
     eng = get_engine(hg.projectionmodel, hg.composite)
@@ -742,7 +830,6 @@ def main():
             traffic = None
     total_macs = whole_path_macs(macs, per, 3)
 
-    log(f"[bench] headline {value:.0f} explained samples/s ({ms:.3f} ms/step); secondaries next")
     # ---- secondary: standard LRP (C2, bs=64) ----
     c2 = bs64 = None
     if "c2" in legs:
@@ -828,54 +915,28 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
         if rank != 0:
-            return
+            return None
     cpu = cpu_drsa = None
     if not args.no_cpu_baseline and rank == 0:
         cpu = cpu_baseline()
         cpu_drsa = cpu_drsa_baseline()
 
-    if rank == 0:
-        out = {
-            "metric": "explained samples/sec (LRP+DRSA k=4)",
-            "value": value,
-            "unit": "explained samples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms,
-            "rank_ms_per_step": rank_ms,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp32",
-            "data": "synthetic (seeded log-mel-like 128x128 batches; random-init GTZAN-128 weights, "
-                    "torch.manual_seed(0); U = ortho_group.rvs(64) seed 42)",
-            "config": {"workload": "GTZAN-128 HeatmapGenerator: LRP (WSquare/Gamma/Epsilon name map) + DRSA "
-                                   "subspace heatmaps, K=4 at layer j=7 (conv3 block, d=64), sorted info dict",
-                       "standard_heatmap": "sum of the K concept heatmaps (standard='sum'; exact reformulation, "
-                                           "bit-exact vs the oracle); the reference's clone-0 form: "
-                                           "secondary.clone_mode; with the numpy info D2H: secondary.to_host",
-                       "global_batch": B * world, "per_gpu_batch": B, "input": "128x128 log-mel",
-                       "parallelism": f"data-parallel x{world} (no collective on the data path)",
-                       "launch": ("torchrun" if os.environ.get("TORCHELASTIC_RUN_ID") else
-                                  "bench.py --gpus (own launcher)" if world > 1 else "single process"),
-                       "one_device_rehearsal": one_dev, "backend": backend if world > 1 else None},
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": dom_ach, "peak": FP32_MFMA_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": dom_ach / FP32_MFMA_PEAK_TFLOPS, "traffic": traffic,
-                         "traffic_source": traffic_src},
-            "whole_path": {"algorithmic_gflop_per_sample": 2.0 * total_macs / B / 1e9,
-                           "achieved_tflops": 2.0 * total_macs * value / B / world / 1e12},
-            "kernels": kernels,
-            "secondary": {"standard_lrp_c2_bs64_samples_per_s": c2 and c2 * world,
-                          "explained_samples_per_s_bs64": bs64 and bs64 * world, "drsa": drsa,
-                          "drsa_sharded": drsa_sharded, "drsa_rank_local_pipeline": pipeline,
-                          "drsa_joint_c5": joint, "vggish_lrp": vgg,
-                          "drsa_grid_task_parallel": grid, "logmel_frontend": frontend, "to_host": to_host,
-                          "clone_mode": clone_mode,
-                          "cpu_baseline_drsa_c3": cpu_drsa},
-            "cpu_baseline": cpu,
-        }
-        print(json.dumps(out), flush=True)
+    return {
+        "roofline": {"bound": "mfma", "kernel": dom, "achieved": dom_ach, "peak": FP32_MFMA_PEAK_TFLOPS,
+                     "unit": "TFLOP/s", "frac": dom_ach / FP32_MFMA_PEAK_TFLOPS, "traffic": traffic,
+                     "traffic_source": traffic_src},
+        "whole_path": {"algorithmic_gflop_per_sample": 2.0 * total_macs / B / 1e9,
+                       "achieved_tflops": 2.0 * total_macs * value / B / world / 1e12},
+        "kernels": kernels,
+        "secondary": {"standard_lrp_c2_bs64_samples_per_s": c2 and c2 * world,
+                      "explained_samples_per_s_bs64": bs64 and bs64 * world, "drsa": drsa,
+                      "drsa_sharded": drsa_sharded, "drsa_rank_local_pipeline": pipeline,
+                      "drsa_joint_c5": joint, "vggish_lrp": vgg,
+                      "drsa_grid_task_parallel": grid, "logmel_frontend": frontend, "to_host": to_host,
+                      "clone_mode": clone_mode,
+                      "cpu_baseline_drsa_c3": cpu_drsa},
+        "cpu_baseline": cpu,
+    }
 
 
 if __name__ == "__main__":

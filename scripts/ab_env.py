@@ -15,7 +15,7 @@ for combo in itertools.product(*[v.split(",") for _, v in toggles]):
     env = dict(os.environ)
     for (k, _), v in zip(toggles, combo):
         env[k] = v
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-drsa", *bench_args],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--no-drsa", *bench_args],
                        capture_output=True, text=True, env=env, timeout=600)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if not line:

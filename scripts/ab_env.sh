@@ -5,5 +5,5 @@ cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/$1; VAR=$2; shift 2
 mkdir -p $O
 for v in "$@"; do
-  env $VAR=$v timeout -k 10 300 python bench.py --no-cpu-baseline --no-drsa > $O/bench_$v.json 2> $O/bench_$v.err
+  env $VAR=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-drsa > $O/bench_$v.json 2> $O/bench_$v.err
 done

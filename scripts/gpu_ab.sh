@@ -10,8 +10,8 @@ if [ -n "$T" ]; then
   timeout -k 10 900 python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu $T > $O/pytest_gpu.log 2>&1
 fi
 for i in 1 2; do
-  env $EA timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > $O/bench_A$i.json 2> $O/bench_A$i.err
-  env $EB timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > $O/bench_B$i.json 2> $O/bench_B$i.err
+  env $EA timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > $O/bench_A$i.json 2> $O/bench_A$i.err
+  env $EB timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > $O/bench_B$i.json 2> $O/bench_B$i.err
 done
 python - "$O" <<'PY'
 import json, sys, glob, os

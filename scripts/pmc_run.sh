@@ -8,7 +8,7 @@ OUT=${1:-gpurun_out/pmc}
 mkdir -p $OUT
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_$c -o run -- \
-    python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-drsa --tag-order $OUT/tags_$c.json \
+    python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-drsa --tag-order $OUT/tags_$c.json \
     > $OUT/pmc_$c.log 2>&1
 done
 cp $OUT/tags_FETCH_SIZE.json $OUT/tags.json

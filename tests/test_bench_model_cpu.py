@@ -47,6 +47,45 @@ def test_kernel_macs_launched_only():
     assert macs["conv_bwd:features.3"] == 512 * 4 * 64 * 64 * 32 * 32 * 9
 
 
+def test_dump_outputs_whole_batch_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array as float32 (integers: float64); over the byte budget, the same
+    seeded ascending sample of batch rows from every array, identical from call to call."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    out = {"standard_heatmaps": torch.randn(12, 1, 8, 8, generator=g), "standard_relevance": torch.randn(12, generator=g),
+           "mask": torch.randint(0, 4, (12, 4), generator=g)}
+    bench.dump_outputs(str(tmp_path / "all"), out)
+    for k, v in out.items():
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == (np.float32 if v.is_floating_point() else np.float64)
+        assert np.array_equal(a, v.numpy())
+    row_bytes = 4 * 64 + 4 + 8 * 4
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 5 * row_bytes + 3)
+    bench.dump_outputs(str(tmp_path / "s1"), out)
+    bench.dump_outputs(str(tmp_path / "s2"), out)
+    rel = np.load(tmp_path / "s1" / "standard_relevance.npy")
+    assert rel.shape == (5,)
+    rows = [int(np.flatnonzero(out["standard_relevance"].numpy() == r)[0]) for r in rel]
+    assert rows == sorted(set(rows))
+    total = 0
+    for k, v in out.items():
+        a = np.load(tmp_path / "s1" / (k + ".npy"))
+        assert np.array_equal(a, v.numpy()[rows]) and np.array_equal(a, np.load(tmp_path / "s2" / (k + ".npy")))
+        total += a.nbytes
+    assert total <= bench.DUMP_BUDGET_BYTES
+
+
+@pytest.mark.parametrize("argv", [["--legs", "grid"], ["--tag-order", "tags.json"], ["--steps", "0"]])
+def test_plain_run_refuses_full_only_options(argv, monkeypatch):
+    """A plain run times the headline only: options of the --full legs are an error, not ignored
+    (argparse exits before any GPU call)."""
+    monkeypatch.setattr("sys.argv", ["bench.py", *argv])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+
+
 def test_whole_path_counts_repeat_launches():
     eng = _gtzan_engine()
     macs = bench.kernel_macs(eng, 8, 4, "sum", launched=["conv_fwd:features.3", "heatmap_sort"])
