@@ -34,8 +34,8 @@
 #define DRSA_PARTIAL_STAMP(slot)
 #endif
 
-#include <stdlib.h>
 #include <type_traits>
+#include <vector>
 
 namespace {
 
@@ -1330,6 +1330,37 @@ __global__ __launch_bounds__(fin_threads<DP>()) void polar_kernel(const float* _
 // ---------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------
+// The template dispatch: f(std::integral_constant<int, V>{}) for the run-time padded size / concept
+// width.  A value outside the set (and so outside the instantiated kernels) is DRSA_EUNSUPPORTED.
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+template <class F>
+int with_dp(int DP, F&& f) {
+  switch (DP) {
+    case 16: return f(Int<16>{});
+    case 32: return f(Int<32>{});
+    case 64: return f(Int<64>{});
+    case 128: return f(Int<128>{});
+  }
+  return DRSA_EUNSUPPORTED;
+}
+
+// a concept is at most as wide as the padded problem: no DKp = 32 at DP = 16, no DKp = 64 below DP = 64
+template <int DP, class F>
+int with_dkp(int DKp, F&& f) {
+  switch (DKp) {
+    case 1: return f(Int<1>{});
+    case 2: return f(Int<2>{});
+    case 4: return f(Int<4>{});
+    case 8: return f(Int<8>{});
+    case 16: return f(Int<16>{});
+    case 32: if constexpr (DP >= 32) return f(Int<32>{}); break;
+    case 64: if constexpr (DP >= 64) return f(Int<64>{}); break;
+  }
+  return DRSA_EUNSUPPORTED;
+}
+
 struct PartialPlan {
   int grid;
   int64_t rb_total;
@@ -1355,41 +1386,25 @@ int launch_partial(const void* A, const void* C, int64_t N, const Geom& g, const
   return DRSA_OK;
 }
 
-template <int DP, int DT>
-int dispatch_partial_dp(const void* A, const void* C, int64_t N, const Geom& g, const float* U, float* partials,
-                        const PartialPlan& pl, hipStream_t s) {
-  switch (g.DKp) {
-    case 1: return launch_partial<DP, 1, DT>(A, C, N, g, U, partials, pl, s);
-    case 2: return launch_partial<DP, 2, DT>(A, C, N, g, U, partials, pl, s);
-    case 4: return launch_partial<DP, 4, DT>(A, C, N, g, U, partials, pl, s);
-    case 8: return launch_partial<DP, 8, DT>(A, C, N, g, U, partials, pl, s);
-    case 16: return launch_partial<DP, 16, DT>(A, C, N, g, U, partials, pl, s);
-    case 32: if constexpr (DP >= 32) return launch_partial<DP, 32, DT>(A, C, N, g, U, partials, pl, s); break;
-    case 64: if constexpr (DP >= 64) return launch_partial<DP, 64, DT>(A, C, N, g, U, partials, pl, s); break;
-    default: break;
-  }
-  drsa::set_error("drsa_partial: unsupported d=%d K=%d", g.d, g.K);
-  return DRSA_EUNSUPPORTED;
-}
-
+// no 16-bit A, C at DP = 16 (the 16-bit MFMA tiles are 32 deep)
 int dispatch_partial(const void* A, const void* C, int64_t N, const Geom& g, const float* U, float* partials,
                      const PartialPlan& pl, hipStream_t s, int dt) {
-  switch (g.DP) {
-    case 16:
-      if (dt) break;
-      return dispatch_partial_dp<16, 0>(A, C, N, g, U, partials, pl, s);
-    case 32: return dt == 1 ? dispatch_partial_dp<32, 1>(A, C, N, g, U, partials, pl, s)
-                  : dt == 2 ? dispatch_partial_dp<32, 2>(A, C, N, g, U, partials, pl, s)
-                            : dispatch_partial_dp<32, 0>(A, C, N, g, U, partials, pl, s);
-    case 64: return dt == 1 ? dispatch_partial_dp<64, 1>(A, C, N, g, U, partials, pl, s)
-                  : dt == 2 ? dispatch_partial_dp<64, 2>(A, C, N, g, U, partials, pl, s)
-                            : dispatch_partial_dp<64, 0>(A, C, N, g, U, partials, pl, s);
-    case 128: return dt == 1 ? dispatch_partial_dp<128, 1>(A, C, N, g, U, partials, pl, s)
-                   : dt == 2 ? dispatch_partial_dp<128, 2>(A, C, N, g, U, partials, pl, s)
-                             : dispatch_partial_dp<128, 0>(A, C, N, g, U, partials, pl, s);
-  }
-  drsa::set_error("drsa_partial: unsupported d=%d K=%d%s", g.d, g.K, dt == 1 ? " (bf16)" : dt == 2 ? " (fp16)" : "");
-  return DRSA_EUNSUPPORTED;
+  const int rc = with_dp(g.DP, [&](auto dp) -> int {
+    constexpr int DP = decltype(dp)::value;
+    return with_dkp<DP>(g.DKp, [&](auto dkp) -> int {
+      constexpr int DKP = decltype(dkp)::value;
+      if constexpr (DP >= 32) {
+        if (dt == 1) return launch_partial<DP, DKP, 1>(A, C, N, g, U, partials, pl, s);
+        if (dt == 2) return launch_partial<DP, DKP, 2>(A, C, N, g, U, partials, pl, s);
+      } else if (dt) {
+        return DRSA_EUNSUPPORTED;
+      }
+      return launch_partial<DP, DKP, 0>(A, C, N, g, U, partials, pl, s);
+    });
+  });
+  if (rc == DRSA_EUNSUPPORTED)
+    drsa::set_error("drsa_partial: unsupported d=%d K=%d%s", g.d, g.K, dt == 1 ? " (bf16)" : dt == 2 ? " (fp16)" : "");
+  return rc;
 }
 
 template <int DP>
@@ -1406,13 +1421,10 @@ int launch_finish(const float* gs, double n_total, const Geom& g, const float* U
 
 int dispatch_finish(const float* gs, double n_total, const Geom& g, const float* U, float* U_out, float* f_out,
                     int* counter, int by_counter, int mode, float tol, int max_iter, int* iters, hipStream_t s) {
-  switch (g.DP) {
-    case 16: return launch_finish<16>(gs, n_total, g, U, U_out, f_out, counter, by_counter, mode, tol, max_iter, iters, s);
-    case 32: return launch_finish<32>(gs, n_total, g, U, U_out, f_out, counter, by_counter, mode, tol, max_iter, iters, s);
-    case 64: return launch_finish<64>(gs, n_total, g, U, U_out, f_out, counter, by_counter, mode, tol, max_iter, iters, s);
-    case 128: return launch_finish<128>(gs, n_total, g, U, U_out, f_out, counter, by_counter, mode, tol, max_iter, iters, s);
-  }
-  return DRSA_EUNSUPPORTED;
+  return with_dp(g.DP, [&](auto dp) -> int {
+    return launch_finish<decltype(dp)::value>(gs, n_total, g, U, U_out, f_out, counter, by_counter, mode, tol, max_iter,
+                                              iters, s);
+  });
 }
 
 constexpr float kPolarTol = 4e-7f;
@@ -1459,15 +1471,13 @@ int fused_step(const float* A, const float* C, int64_t N, double n_total, const 
                float* gs_out, const float* U, float* U_out, float* f_out, int* counter, void* ws, hipStream_t s) {
   const PartialPlan pl = plan_partial(N);
   float* partials = (float*)ws;
-  int rc = DRSA_EUNSUPPORTED;
-  switch (g.DKp) {
-    case 1: rc = launch_fused<1>(A, C, N, n_total, g, gs, U, U_out, f_out, counter, partials, pl, s); break;
-    case 2: rc = launch_fused<2>(A, C, N, n_total, g, gs, U, U_out, f_out, counter, partials, pl, s); break;
-    case 4: rc = launch_fused<4>(A, C, N, n_total, g, gs, U, U_out, f_out, counter, partials, pl, s); break;
-    case 8: rc = launch_fused<8>(A, C, N, n_total, g, gs, U, U_out, f_out, counter, partials, pl, s); break;
-    case 16: rc = launch_fused<16>(A, C, N, n_total, g, gs, U, U_out, f_out, counter, partials, pl, s); break;
-    default: drsa::set_error("drsa fused step: unsupported d=%d K=%d", g.d, g.K); return rc;
-  }
+  const int rc = with_dkp<64>(g.DKp, [&](auto dkp) -> int {
+    constexpr int DKP = decltype(dkp)::value;
+    if constexpr (DKP <= 16)   // fused_ok
+      return launch_fused<DKP>(A, C, N, n_total, g, gs, U, U_out, f_out, counter, partials, pl, s);
+    return DRSA_EUNSUPPORTED;
+  });
+  if (rc == DRSA_EUNSUPPORTED) drsa::set_error("drsa fused step: unsupported d=%d K=%d", g.d, g.K);
   if (rc) return rc;
   return launch_reduce(partials, pl, g, gs_out, s);
 }
@@ -1480,14 +1490,63 @@ size_t ws_bytes(int64_t N, const Geom& g) {
   return g.DP == 128 ? base + 256 + sizeof(CoopXchg) : base;
 }
 
+// The argument check of every entry point (`who` in front of each message): the geometry is
+// supported and N > 0, plus what `need` asks for.  Sets g; DRSA_EINVAL with the error set otherwise.
+enum : unsigned {
+  kEmptyOk = 1,   // N = 0 is allowed (and then needs neither workspace nor alignment)
+  kWs = 2,        // ws holds ws_bytes(N, g)
+  kAlign = 4,     // A and C are 16-byte aligned (float4 loads)
+  kNoAlias = 8,   // U != U_out
+  kDtype = 16,    // dtype is 0 (fp32), or 1 / 2 (bf16 / fp16) at padded d >= 32
+};
+
+struct ProblemArgs {   // what the needs look at
+  const void *U = nullptr, *U_out = nullptr, *ws = nullptr;
+  size_t ws_size = 0;
+  const void *A = nullptr, *C = nullptr;
+  int dtype = 0;
+};
+
+int check_problem(const char* who, Geom& g, int d, int K, int64_t N, unsigned need, const ProblemArgs& a = {}) {
+  g = geom(d, K);
+  DRSA_REQUIRE(g.ok, "%s: unsupported d=%d K=%d (need d <= 128, K | d, padded concept width <= 64 and "
+               "K * padded width <= 128)", who, d, K);
+  DRSA_REQUIRE(N > 0 || (N == 0 && (need & kEmptyOk)), "%s: N must be %s 0", who, (need & kEmptyOk) ? ">=" : ">");
+  DRSA_REQUIRE(!(need & kDtype) || a.dtype == 0 || ((a.dtype == 1 || a.dtype == 2) && g.DP >= 32),
+               "%s: dtype must be 0 (fp32) or 1/2 (bf16/fp16, padded d >= 32)", who);
+  DRSA_REQUIRE(!(need & kNoAlias) || a.U != a.U_out, "%s: U and U_out must not alias", who);
+  if (N == 0) return DRSA_OK;
+  DRSA_REQUIRE(!(need & kWs) || (a.ws && a.ws_size >= ws_bytes(N, g)), "%s: workspace too small", who);
+  DRSA_REQUIRE(!(need & kAlign) || (((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.C % 16) == 0),
+               "%s: A/C must be 16B aligned", who);
+  return DRSA_OK;
+}
+
+// one drsa_amd_problem_t of run_multi / run_batched
+int check_run_problem(const char* entry, int p, const drsa_amd_problem_t& q, Geom& g, unsigned need) {
+  char who[64];
+  snprintf(who, sizeof(who), "%s: problem %d", entry, p);
+  const ProblemArgs a{q.U_io, q.U_tmp, q.ws, q.ws_size, q.A, q.C, q.dtype};
+  if (int rc = check_problem(who, g, q.d, q.K, q.N, need | kWs, a)) return rc;
+  DRSA_REQUIRE(q.A && q.C && q.U_io && q.U_tmp && q.f_traj && q.counter, "%s: null pointer", who);
+  return DRSA_OK;
+}
+
+// both fused-step entry points: DP = 64 geometry, the N local rows of N_total, workspace, alignment
+int check_fused(const char* who, Geom& g, const void* A, const void* C, int64_t N, int d, int K, int64_t N_total,
+                const void* U, const void* U_out, const void* ws, size_t ws_size) {
+  if (int rc = check_problem(who, g, d, K, N, kNoAlias | kWs | kAlign, {U, U_out, ws, ws_size, A, C})) return rc;
+  DRSA_REQUIRE(fused_ok(g), "%s: unsupported d=%d K=%d (drsa_amd_drsa_fused_supported)", who, d, K);
+  DRSA_REQUIRE(N_total >= N, "%s: need N <= N_total", who);
+  return DRSA_OK;
+}
+
 int partial_impl(const void* A, const void* C, int64_t N, int d, int K, const float* U, float* gs_out, void* ws,
                  size_t ws_size, void* stream, int dtype) {
-  const Geom g = geom(d, K);
-  DRSA_REQUIRE(g.ok, "drsa_partial: unsupported d=%d K=%d (need d <= 128, K | d, padded concept width <= 64 and "
-               "K * padded width <= 128)", d, K);
-  DRSA_REQUIRE(N >= 0, "drsa_partial: N < 0");
-  DRSA_REQUIRE(dtype == 0 || ((dtype == 1 || dtype == 2) && g.DP >= 32),
-               "drsa_partial: dtype must be 0 (fp32) or 1/2 (bf16/fp16, padded d >= 32)");
+  Geom g;
+  if (int rc = check_problem("drsa_partial", g, d, K, N, kEmptyOk | kDtype | kWs | kAlign,
+                             {U, nullptr, ws, ws_size, A, C, dtype}))
+    return rc;
   DRSA_REQUIRE(A && C && U && gs_out, "drsa_partial: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const size_t E = slab_floats(g);
@@ -1495,8 +1554,6 @@ int partial_impl(const void* A, const void* C, int64_t N, int d, int K, const fl
     DRSA_HIP(hipMemsetAsync(gs_out, 0, E * sizeof(float), s));
     return DRSA_OK;
   }
-  DRSA_REQUIRE(ws && ws_size >= ws_bytes(N, g), "drsa_partial: workspace too small");
-  DRSA_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)C % 16) == 0, "drsa_partial: A/C must be 16B aligned");
   const PartialPlan pl = plan_partial(N);
   float* partials = (float*)ws;
   int rc = dispatch_partial(A, C, N, g, U, partials, pl, s, dtype);
@@ -1525,9 +1582,10 @@ int coop_reset(CoopXchg* xc, hipStream_t s) {
 long long g_coop_spin_ticks = kCoopSpinTicks;
 int g_coop_min_polls = kCoopMinPolls;
 
+// a capture is open on s (never asked of the null stream)
 bool stream_capturing(hipStream_t s) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+  return s && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
 }
 
 // reads the run's sticky status word back (synchronises stream s); DRSA_ETIMEOUT if it is set
@@ -1563,6 +1621,41 @@ int step_finish(const float* gs, double n_total, const Geom& g, const float* U, 
                          s);
 }
 
+// the captured pair of steps and its executable, released on every path out of run_steps
+struct StepGraph {
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  ~StepGraph() {
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+  }
+};
+
+// The step loop of drsa_run, run_multi and run_batched on stream s.  pair() records two steps
+// U_io -> U_tmp -> U_io, tail() one step and the copy of U_tmp home, final() the objective at U_S.
+// With use_graph, steps >= 2 and no capture already open on s, pair() is captured once into a
+// hipGraph and replayed steps / 2 times; otherwise (also inside a caller's capture) the pairs are
+// recorded one after the other.  Then the odd tail and the final objective.
+template <class Pair, class Tail, class Final>
+int run_steps(hipStream_t s, int steps, bool use_graph, Pair&& pair, Tail&& tail, Final&& final) {
+  int done = 0;
+  if (use_graph && steps >= 2 && !stream_capturing(s)) {
+    StepGraph g;
+    DRSA_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    const int rc = pair();
+    const hipError_t ce = hipStreamEndCapture(s, &g.graph);   // also after a failed body: the capture must end
+    if (rc) return rc;
+    DRSA_HIP(ce);
+    DRSA_HIP(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
+    for (; done + 2 <= steps; done += 2) DRSA_HIP(hipGraphLaunch(g.exec, s));
+  }
+  for (; done + 2 <= steps; done += 2)
+    if (int rc = pair()) return rc;
+  if (done < steps)
+    if (int rc = tail()) return rc;
+  return final();
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1577,11 +1670,11 @@ int drsa_amd_debug_coop_stamps(unsigned long long* host_out) {
 #endif
 
 int drsa_amd_drsa_coop_status(const void* ws, int64_t N, int d, int K, int* status_out, void* stream) {
-  const Geom g = geom(d, K);
-  DRSA_REQUIRE(g.ok && N > 0, "drsa_coop_status: unsupported d=%d K=%d or N <= 0", d, K);
+  Geom g;
+  if (int rc = check_problem("drsa_coop_status", g, d, K, N, 0)) return rc;
   DRSA_REQUIRE(ws && status_out, "drsa_coop_status: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  DRSA_REQUIRE(!(s && stream_capturing(s)), "drsa_coop_status: the stream is being captured");
+  DRSA_REQUIRE(!stream_capturing(s), "drsa_coop_status: the stream is being captured");
   *status_out = 0;
   const CoopXchg* xc = ws_xchg(const_cast<void*>(ws), N, g);
   if (!xc) return DRSA_OK;
@@ -1632,11 +1725,9 @@ int drsa_amd_drsa_partial_f16(const uint16_t* A, const uint16_t* C, int64_t N, i
 
 int drsa_amd_drsa_finish(const float* gs, int64_t N_total, int d, int K, const float* U, float* U_out,
                          float* f_out, int objective_only, int* iters_out, void* stream) {
-  const Geom g = geom(d, K);
-  DRSA_REQUIRE(g.ok, "drsa_finish: unsupported d=%d K=%d", d, K);
-  DRSA_REQUIRE(N_total > 0, "drsa_finish: N_total must be > 0");
+  Geom g;
+  if (int rc = check_problem("drsa_finish", g, d, K, N_total, objective_only ? 0 : kNoAlias, {U, U_out})) return rc;
   DRSA_REQUIRE(gs && U && f_out && (objective_only || U_out), "drsa_finish: null pointer");
-  DRSA_REQUIRE(objective_only || U != U_out, "drsa_finish: U and U_out must not alias");
   return dispatch_finish(gs, (double)N_total, g, U, U_out, f_out, nullptr, 0, objective_only ? 1 : 0, kPolarTol,
                          kPolarMaxIter, iters_out, (hipStream_t)stream);
 }
@@ -1646,47 +1737,34 @@ int drsa_amd_drsa_fused_supported(int d, int K) { return fused_ok(geom(d, K)) ? 
 int drsa_amd_drsa_fused_step(const float* A, const float* C, int64_t N, int d, int K, const float* gs,
                              int64_t N_total, const float* U, float* U_out, float* f_out, float* gs_out, void* ws,
                              size_t ws_size, void* stream) {
-  const Geom g = geom(d, K);
-  DRSA_REQUIRE(g.ok && fused_ok(g), "drsa_fused_step: unsupported d=%d K=%d (drsa_amd_drsa_fused_supported)", d, K);
-  DRSA_REQUIRE(N > 0 && N_total >= N, "drsa_fused_step: need 0 < N <= N_total");
+  Geom g;
+  if (int rc = check_fused("drsa_fused_step", g, A, C, N, d, K, N_total, U, U_out, ws, ws_size)) return rc;
   DRSA_REQUIRE(A && C && gs && U && U_out && f_out && gs_out, "drsa_fused_step: null pointer");
-  DRSA_REQUIRE(U != U_out, "drsa_fused_step: U and U_out must not alias");
-  DRSA_REQUIRE(ws && ws_size >= ws_bytes(N, g), "drsa_fused_step: workspace too small");
-  DRSA_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)C % 16) == 0, "drsa_fused_step: A/C must be 16B aligned");
   return fused_step(A, C, N, (double)N_total, g, gs, gs_out, U, U_out, f_out, nullptr, ws, (hipStream_t)stream);
 }
 
 int drsa_amd_drsa_fused_step_counted(const float* A, const float* C, int64_t N, int d, int K, const float* gs,
                                      int64_t N_total, const float* U, float* U_out, float* f_traj, int* counter,
                                      float* gs_out, void* ws, size_t ws_size, void* stream) {
-  const Geom g = geom(d, K);
-  DRSA_REQUIRE(g.ok && fused_ok(g), "drsa_fused_step_counted: unsupported d=%d K=%d", d, K);
-  DRSA_REQUIRE(N > 0 && N_total >= N, "drsa_fused_step_counted: need 0 < N <= N_total");
+  Geom g;
+  if (int rc = check_fused("drsa_fused_step_counted", g, A, C, N, d, K, N_total, U, U_out, ws, ws_size)) return rc;
   DRSA_REQUIRE(A && C && gs && U && U_out && f_traj && counter && gs_out, "drsa_fused_step_counted: null pointer");
-  DRSA_REQUIRE(U != U_out, "drsa_fused_step_counted: U and U_out must not alias");
-  DRSA_REQUIRE(ws && ws_size >= ws_bytes(N, g), "drsa_fused_step_counted: workspace too small");
-  DRSA_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)C % 16) == 0, "drsa_fused_step_counted: A/C must be 16B aligned");
   return fused_step(A, C, N, (double)N_total, g, gs, gs_out, U, U_out, f_traj, counter, ws, (hipStream_t)stream);
 }
 
 int drsa_amd_drsa_finish_counted(const float* gs, int64_t N_total, int d, int K, const float* U, float* U_out,
                                  float* f_traj, int* counter, void* stream) {
-  const Geom g = geom(d, K);
-  DRSA_REQUIRE(g.ok, "drsa_finish_counted: unsupported d=%d K=%d", d, K);
-  DRSA_REQUIRE(N_total > 0, "drsa_finish_counted: N_total must be > 0");
+  Geom g;
+  if (int rc = check_problem("drsa_finish_counted", g, d, K, N_total, kNoAlias, {U, U_out})) return rc;
   DRSA_REQUIRE(gs && U && U_out && f_traj && counter, "drsa_finish_counted: null pointer");
-  DRSA_REQUIRE(U != U_out, "drsa_finish_counted: U and U_out must not alias");
   return dispatch_finish(gs, (double)N_total, g, U, U_out, f_traj, counter, 1, 0, kPolarTol, kPolarMaxIter, nullptr,
                          (hipStream_t)stream);
 }
 
 int drsa_amd_drsa_step(const float* A, const float* C, int64_t N, int d, int K, const float* U,
                        float* U_out, float* f_out, void* ws, size_t ws_size, void* stream) {
-  const Geom g = geom(d, K);
-  DRSA_REQUIRE(g.ok, "drsa_step: unsupported d=%d K=%d", d, K);
-  DRSA_REQUIRE(N > 0, "drsa_step: N must be > 0");
-  DRSA_REQUIRE(U != U_out, "drsa_step: U and U_out must not alias");
-  DRSA_REQUIRE(ws && ws_size >= ws_bytes(N, g), "drsa_step: workspace too small");
+  Geom g;
+  if (int rc = check_problem("drsa_step", g, d, K, N, kNoAlias | kWs, {U, U_out, ws, ws_size})) return rc;
   float* gs = ws_gs(ws, N, g);
   int rc = drsa_amd_drsa_partial(A, C, N, d, K, U, gs, ws, ws_size, stream);
   if (rc) return rc;
@@ -1695,10 +1773,8 @@ int drsa_amd_drsa_step(const float* A, const float* C, int64_t N, int d, int K, 
 
 int drsa_amd_drsa_objective(const float* A, const float* C, int64_t N, int d, int K, const float* U,
                             float* f_out, void* ws, size_t ws_size, void* stream) {
-  const Geom g = geom(d, K);
-  DRSA_REQUIRE(g.ok, "drsa_objective: unsupported d=%d K=%d", d, K);
-  DRSA_REQUIRE(N > 0, "drsa_objective: N must be > 0");
-  DRSA_REQUIRE(ws && ws_size >= ws_bytes(N, g), "drsa_objective: workspace too small");
+  Geom g;
+  if (int rc = check_problem("drsa_objective", g, d, K, N, kWs, {U, nullptr, ws, ws_size})) return rc;
   float* gs = ws_gs(ws, N, g);
   int rc = drsa_amd_drsa_partial(A, C, N, d, K, U, gs, ws, ws_size, stream);
   if (rc) return rc;
@@ -1712,17 +1788,12 @@ int drsa_amd_drsa_objective(const float* A, const float* C, int64_t N, int d, in
 int drsa_amd_drsa_run(const float* A, const float* C, int64_t N, int d, int K, float* U_io, float* U_tmp,
                       int steps, float* f_traj, int* counter, void* ws, size_t ws_size, int use_graph,
                       void* stream) {
-  const Geom g = geom(d, K);
-  DRSA_REQUIRE(g.ok, "drsa_run: unsupported d=%d K=%d", d, K);
-  DRSA_REQUIRE(N > 0 && steps >= 0, "drsa_run: bad N/steps");
-  DRSA_REQUIRE(ws && ws_size >= ws_bytes(N, g), "drsa_run: workspace too small");
+  Geom g;
+  if (int rc = check_problem("drsa_run", g, d, K, N, kWs, {U_io, U_tmp, ws, ws_size})) return rc;
+  DRSA_REQUIRE(steps >= 0, "drsa_run: steps < 0");
   DRSA_REQUIRE(A && C && U_io && U_tmp && f_traj && counter, "drsa_run: null pointer");
   hipStream_t s = (hipStream_t)stream;
   float* gs = ws_gs(ws, N, g);
-  // already inside a stream capture (e.g. a torch CUDA graph): record the plain sequence, and leave
-  // the cooperative finish's status check to the caller (drsa_amd_drsa_coop_status)
-  const bool capturing = s && stream_capturing(s);
-  if (capturing) use_graph = 0;
   DRSA_HIP(hipMemsetAsync(counter, 0, sizeof(int), s));
   CoopXchg* xc = ws_xchg(ws, N, g);
   if (int rc = coop_reset(xc, s)) return rc;
@@ -1739,44 +1810,28 @@ int drsa_amd_drsa_run(const float* A, const float* C, int64_t N, int d, int K, f
     if (rc) return rc;
     return step_finish(gs, (double)N, g, Uin, Uout, f_traj, counter, xc, s);
   };
-  int done = 0;
-  if (use_graph && steps >= 2) {
-    // capture U_io -> U_tmp -> U_io
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    DRSA_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    int rc1 = one(U_io, U_tmp);
-    int rc2 = rc1 ? rc1 : one(U_tmp, U_io);
-    hipError_t ce = hipStreamEndCapture(s, &graph);
-    if (rc2) { if (graph) (void)hipGraphDestroy(graph); return rc2; }
-    DRSA_HIP(ce);
-    hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    if (ie != hipSuccess) { (void)hipGraphDestroy(graph); DRSA_HIP(ie); }
-    for (; done + 2 <= steps; done += 2) {
-      hipError_t le = hipGraphLaunch(exec, s);
-      if (le != hipSuccess) { (void)hipGraphExecDestroy(exec); (void)hipGraphDestroy(graph); DRSA_HIP(le); }
-    }
-    (void)hipGraphExecDestroy(exec);
-    (void)hipGraphDestroy(graph);
-  }
-  for (; done + 2 <= steps; done += 2) {
+  auto pair = [&]() -> int {
     int rc = one(U_io, U_tmp);
-    if (rc) return rc;
-    rc = one(U_tmp, U_io);
-    if (rc) return rc;
-  }
-  if (done < steps) {
-    int rc = one(U_io, U_tmp);
-    if (rc) return rc;
+    return rc ? rc : one(U_tmp, U_io);
+  };
+  auto tail = [&]() -> int {
+    if (int rc = one(U_io, U_tmp)) return rc;
     DRSA_HIP(hipMemcpyAsync(U_io, U_tmp, (size_t)d * d * sizeof(float), hipMemcpyDeviceToDevice, s));
-    ++done;
-  }
-  // final objective -> f_traj[steps]
-  if (!fused) {
-    int rc = drsa_amd_drsa_partial(A, C, N, d, K, U_io, gs, ws, ws_size, stream);
-    if (rc) return rc;
-  }
-  int rc = dispatch_finish(gs, (double)N, g, U_io, nullptr, f_traj, counter, 1, 1, kPolarTol, kPolarMaxIter, nullptr, s);
+    return DRSA_OK;
+  };
+  auto final = [&]() -> int {   // f(U_S) -> f_traj[steps]
+    if (!fused) {
+      int rc = drsa_amd_drsa_partial(A, C, N, d, K, U_io, gs, ws, ws_size, stream);
+      if (rc) return rc;
+    }
+    return dispatch_finish(gs, (double)N, g, U_io, nullptr, f_traj, counter, 1, 1, kPolarTol, kPolarMaxIter, nullptr,
+                           s);
+  };
+  // inside a caller's stream capture (e.g. a torch CUDA graph) this records the plain sequence and
+  // leaves the cooperative finish's status check to the caller (drsa_amd_drsa_coop_status).
+  // use_graph on the null stream is attempted (the capture fails with HIP's error).
+  const bool capturing = stream_capturing(s);
+  int rc = run_steps(s, steps, use_graph != 0, pair, tail, final);
   if (rc || capturing || steps == 0) return rc;
   return coop_check(xc, s, "drsa_run");
 }
@@ -1789,18 +1844,12 @@ int drsa_amd_drsa_run(const float* A, const float* C, int64_t N, int d, int K, f
 int drsa_amd_drsa_run_multi(int P, const drsa_amd_problem_t* probs, int steps, int use_graph, void* stream) {
   DRSA_REQUIRE(P >= 1 && P <= 64 && probs, "drsa_run_multi: P must be in [1, 64]");
   DRSA_REQUIRE(steps >= 0, "drsa_run_multi: steps < 0");
-  for (int p = 0; p < P; ++p) {
-    const drsa_amd_problem_t& q = probs[p];
-    const Geom g = geom(q.d, q.K);
-    DRSA_REQUIRE(g.ok, "drsa_run_multi: problem %d unsupported d=%d K=%d", p, q.d, q.K);
-    DRSA_REQUIRE(q.N > 0 && q.A && q.C && q.U_io && q.U_tmp && q.f_traj && q.counter && q.ws,
-                 "drsa_run_multi: problem %d has null pointers or N <= 0", p);
-    DRSA_REQUIRE(q.ws_size >= ws_bytes(q.N, g), "drsa_run_multi: problem %d workspace too small", p);
-    DRSA_REQUIRE(q.dtype == 0 || ((q.dtype == 1 || q.dtype == 2) && g.DP >= 32),
-                 "drsa_run_multi: problem %d: dtype must be 0 (fp32) or 1/2 (bf16/fp16, padded d >= 32)", p);
-  }
   bool all_f32 = true;
-  for (int p = 0; p < P; ++p) all_f32 = all_f32 && probs[p].dtype == 0;
+  for (int p = 0; p < P; ++p) {
+    Geom g;
+    if (int rc = check_run_problem("drsa_run_multi", p, probs[p], g, kDtype)) return rc;
+    all_f32 = all_f32 && probs[p].dtype == 0;
+  }
   if (all_f32 && (P == 1 || !use_graph || steps < 2)) {
     for (int p = 0; p < P; ++p) {
       const drsa_amd_problem_t& q = probs[p];
@@ -1811,10 +1860,6 @@ int drsa_amd_drsa_run_multi(int P, const drsa_amd_problem_t* probs, int steps, i
     return DRSA_OK;
   }
   hipStream_t s = (hipStream_t)stream;
-  // inside a caller's stream capture (a torch CUDA graph of the whole run): record the forked plain
-  // sequence into it (no graph of our own, no host synchronisation, no status read-back)
-  const bool capturing = s && stream_capturing(s);
-  if (capturing) use_graph = 0;
   // side streams and fork/join events come from a per-thread, per-device pool that lives as long
   // as the thread: a captured graph's forks must not be destroyed before the capture ends
   struct SidePool {
@@ -1827,26 +1872,13 @@ int drsa_amd_drsa_run_multi(int P, const drsa_amd_problem_t* probs, int steps, i
   DRSA_HIP(hipGetDevice(&dev));
   DRSA_REQUIRE(dev >= 0 && dev < 16, "drsa_run_multi: device index %d >= 16", dev);
   SidePool& pool = pools[dev];
-  hipStream_t* side = pool.st;
-  hipEvent_t* ev_join = pool.join;
-  int rc = DRSA_OK;
-  auto cleanup = [&]() {};
-  auto hip_ok = [&](hipError_t e, const char* what) -> bool {
-    if (e == hipSuccess) return true;
-    drsa::set_error("drsa_run_multi: %s: %s", what, hipGetErrorString(e));
-    rc = (int)e;
-    return false;
-  };
-  if (!pool.fork && !hip_ok(hipEventCreateWithFlags(&pool.fork, hipEventDisableTiming), "event")) return rc;
-  hipEvent_t ev_fork = pool.fork;
+  if (!pool.fork) DRSA_HIP(hipEventCreateWithFlags(&pool.fork, hipEventDisableTiming));
   for (int p = 0; p < P; ++p) {
-    if ((!side[p] && !hip_ok(hipStreamCreateWithFlags(&side[p], hipStreamNonBlocking), "stream")) ||
-        (!ev_join[p] && !hip_ok(hipEventCreateWithFlags(&ev_join[p], hipEventDisableTiming), "event"))) {
-      return rc;
-    }
+    if (!pool.st[p]) DRSA_HIP(hipStreamCreateWithFlags(&pool.st[p], hipStreamNonBlocking));
+    if (!pool.join[p]) DRSA_HIP(hipEventCreateWithFlags(&pool.join[p], hipEventDisableTiming));
     const drsa_amd_problem_t& q = probs[p];
-    if (!hip_ok(hipMemsetAsync(q.counter, 0, sizeof(int), s), "memset")) { cleanup(); return rc; }
-    if (int r = coop_reset(ws_xchg(q.ws, q.N, geom(q.d, q.K)), s)) { cleanup(); return r; }
+    DRSA_HIP(hipMemsetAsync(q.counter, 0, sizeof(int), s));
+    if (int rc = coop_reset(ws_xchg(q.ws, q.N, geom(q.d, q.K)), s)) return rc;
   }
   // one step of problem p on stream st: U_in -> U_out, f -> f_traj[counter++]
   auto one = [&](int p, hipStream_t st, const float* Uin, float* Uout) -> int {
@@ -1857,68 +1889,36 @@ int drsa_amd_drsa_run_multi(int P, const drsa_amd_problem_t* probs, int steps, i
     if (r) return r;
     return step_finish(gs, (double)q.N, g, Uin, Uout, q.f_traj, q.counter, ws_xchg(q.ws, q.N, g), st);
   };
-  // fork -> per-problem body -> join, captured from stream s
-  auto forked = [&](int nsteps_body, bool final_objective) -> int {
-    if (!hip_ok(hipEventRecord(ev_fork, s), "record")) return rc;
+  // fork from s -> per problem, on its side stream: nsteps steps (an odd count ends in U_tmp and is
+  // copied home), then the final objective if asked for -> join into s
+  auto forked = [&](int nsteps, bool final_objective) -> int {
+    DRSA_HIP(hipEventRecord(pool.fork, s));
     for (int p = 0; p < P; ++p) {
-      if (!hip_ok(hipStreamWaitEvent(side[p], ev_fork, 0), "wait")) return rc;
       const drsa_amd_problem_t& q = probs[p];
-      for (int k = 0; k < nsteps_body; ++k) {
-        int r = (k % 2 == 0) ? one(p, side[p], q.U_io, q.U_tmp) : one(p, side[p], q.U_tmp, q.U_io);
-        if (r) return r;
-      }
-      if (final_objective) {
-        int r = one(p, side[p], q.U_io, nullptr);
-        if (r) return r;
-      }
-      if (!hip_ok(hipEventRecord(ev_join[p], side[p]), "record")) return rc;
-      if (!hip_ok(hipStreamWaitEvent(s, ev_join[p], 0), "wait")) return rc;
+      hipStream_t st = pool.st[p];
+      DRSA_HIP(hipStreamWaitEvent(st, pool.fork, 0));
+      for (int k = 0; k < nsteps; ++k)
+        if (int r = (k % 2 == 0) ? one(p, st, q.U_io, q.U_tmp) : one(p, st, q.U_tmp, q.U_io)) return r;
+      if (nsteps & 1)
+        DRSA_HIP(hipMemcpyAsync(q.U_io, q.U_tmp, (size_t)q.d * q.d * sizeof(float), hipMemcpyDeviceToDevice, st));
+      if (final_objective)
+        if (int r = one(p, st, q.U_io, nullptr)) return r;
+      // Every side chain joins back into s before the call returns, whatever the geometry or step
+      // count, and nothing else orders the side streams' work: a caller (or a caching allocator)
+      // that frees or reuses A, C, U, f_traj or the workspaces in stream order on s after this call
+      // is safe only because of this join.  Keep it on every path that put work on a side stream.
+      DRSA_HIP(hipEventRecord(pool.join[p], st));
+      DRSA_HIP(hipStreamWaitEvent(s, pool.join[p], 0));
     }
     return DRSA_OK;
   };
-  int done = 0;
-  if (use_graph && steps >= 2) {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    if (!hip_ok(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal), "capture")) { cleanup(); return rc; }
-    int rbody = forked(2, false);
-    hipError_t ce = hipStreamEndCapture(s, &graph);
-    if (rbody || !hip_ok(ce, "end capture") ||
-        !hip_ok(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0), "instantiate")) {
-      if (graph) (void)hipGraphDestroy(graph);
-      cleanup();
-      return rbody ? rbody : rc;
-    }
-    for (; done + 2 <= steps; done += 2)
-      if (!hip_ok(hipGraphLaunch(exec, s), "graph launch")) break;
-    (void)hipGraphExecDestroy(exec);
-    (void)hipGraphDestroy(graph);
-    if (rc) { cleanup(); return rc; }
-  } else {
-    for (; done + 2 <= steps; done += 2) {
-      int r = forked(2, false);
-      if (r) { cleanup(); return r; }
-    }
-  }
-  // odd tail step + final objective, eager on the forked streams
-  if (done < steps) {
-    if (!hip_ok(hipEventRecord(ev_fork, s), "record")) { cleanup(); return rc; }
-    for (int p = 0; p < P; ++p) {
-      const drsa_amd_problem_t& q = probs[p];
-      if (!hip_ok(hipStreamWaitEvent(side[p], ev_fork, 0), "wait")) { cleanup(); return rc; }
-      int r = one(p, side[p], q.U_io, q.U_tmp);
-      if (r) { cleanup(); return r; }
-      if (!hip_ok(hipMemcpyAsync(q.U_io, q.U_tmp, (size_t)q.d * q.d * sizeof(float), hipMemcpyDeviceToDevice,
-                                 side[p]), "copy")) { cleanup(); return rc; }
-      if (!hip_ok(hipEventRecord(ev_join[p], side[p]), "record") || !hip_ok(hipStreamWaitEvent(s, ev_join[p], 0), "wait")) {
-        cleanup();
-        return rc;
-      }
-    }
-  }
-  int r = forked(0, true);
-  if (r) { cleanup(); return r; }
-  if (steps == 0 || capturing) return DRSA_OK;
+  // inside a caller's stream capture (a torch CUDA graph of the whole run) the forked plain sequence
+  // is recorded into it: no graph of our own, no host synchronisation, no status read-back.
+  // use_graph on the null stream is attempted (the capture fails with HIP's error).
+  const bool capturing = stream_capturing(s);
+  int rc = run_steps(s, steps, use_graph != 0, [&] { return forked(2, false); }, [&] { return forked(1, false); },
+                     [&] { return forked(0, true); });
+  if (rc || steps == 0 || capturing) return rc;
   for (int p = 0; p < P; ++p) {
     const drsa_amd_problem_t& q = probs[p];
     if (int rc2 = coop_check(ws_xchg(q.ws, q.N, geom(q.d, q.K)), s, "drsa_run_multi")) return rc2;
@@ -1935,45 +1935,32 @@ int drsa_amd_drsa_run_batched(int P, const drsa_amd_problem_t* probs, int steps,
                               void* stream) {
   DRSA_REQUIRE(P >= 1 && probs, "drsa_run_batched: P must be >= 1");
   DRSA_REQUIRE(steps >= 0, "drsa_run_batched: steps < 0");
-  const Geom g0 = geom(probs[0].d, probs[0].K);
-  DRSA_REQUIRE(g0.ok, "drsa_run_batched: problem 0 unsupported d=%d K=%d", probs[0].d, probs[0].K);
+  Geom g{};   // problem 0's: every problem shares its padded geometry
   bool vec = true;
-  int64_t min_rbt = INT64_MAX;
   for (int p = 0; p < P; ++p) {
     const drsa_amd_problem_t& q = probs[p];
-    const Geom g = geom(q.d, q.K);
-    DRSA_REQUIRE(g.ok && g.DP == g0.DP && g.DKp == g0.DKp,
+    Geom gq;
+    if (int rc = check_run_problem("drsa_run_batched", p, q, gq, kAlign)) return rc;
+    if (p == 0) g = gq;
+    DRSA_REQUIRE(gq.DP == g.DP && gq.DKp == g.DKp,
                  "drsa_run_batched: problem %d (d=%d K=%d) does not share the padded geometry of problem 0", p,
                  q.d, q.K);
     DRSA_REQUIRE(q.dtype == 0, "drsa_run_batched: fp32 problems only (problem %d)", p);
-    DRSA_REQUIRE(q.N > 0 && q.A && q.C && q.U_io && q.U_tmp && q.f_traj && q.counter && q.ws,
-                 "drsa_run_batched: problem %d has null pointers or N <= 0", p);
-    DRSA_REQUIRE(q.ws_size >= ws_bytes(q.N, g), "drsa_run_batched: problem %d workspace too small", p);
-    DRSA_REQUIRE(((uintptr_t)q.A % 16) == 0 && ((uintptr_t)q.C % 16) == 0, "drsa_run_batched: A/C 16B alignment");
     vec = vec && (q.d & 3) == 0;
-    const int64_t rbt = (q.N + 15) / 16;
-    if (rbt < min_rbt) min_rbt = rbt;
   }
   hipStream_t s = (hipStream_t)stream;
-  if (s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    DRSA_REQUIRE(!(hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone),
-                 "drsa_run_batched: not capturable (allocates its descriptor table); use drsa_run_multi");
-  }
+  DRSA_REQUIRE(!stream_capturing(s),
+               "drsa_run_batched: not capturable (allocates its descriptor table); use drsa_run_multi");
   // workgroups per problem: `blocks`, or about 16 waves of one-workgroup-per-CU launches over the
   // chip (the 90-problem grid: one leaf group per workgroup, 36.4k problem-steps/s against 36.0k
   // at two groups); each owns m = ceil(groups / G) whole leaf groups (the result does not depend on it)
   const int cu = drsa::cu_count();
   int Greq = blocks > 0 ? blocks : (16 * cu + P - 1) / P;
   if (Greq < 1) Greq = 1;
-  (void)min_rbt;
-  const Geom& g = g0;
   const size_t E = slab_floats(g), ES = slab_stride(g);
   int G = 1;
-  const bool leafwise = g0.DKp >= 64;          // see drsa_partial_leaf_batched_kernel
-  // descriptor table on the device
-  BatchDesc* hd = (BatchDesc*)malloc(sizeof(BatchDesc) * (size_t)P);
-  DRSA_REQUIRE(hd, "drsa_run_batched: host allocation failed");
+  const bool leafwise = g.DKp >= 64;          // see drsa_partial_leaf_batched_kernel
+  std::vector<BatchDesc> hd((size_t)P);
   for (int p = 0; p < P; ++p) {
     const drsa_amd_problem_t& q = probs[p];
     const Geom gq = geom(q.d, q.K);
@@ -1985,24 +1972,26 @@ int drsa_amd_drsa_run_batched(int P, const drsa_amd_problem_t* probs, int steps,
     hd[p] = BatchDesc{q.A, q.C, q.N, pl.rb_total, q.d, q.K, q.d / q.K, gq.DKp, Gp, pl.grid, m, q.U_io, q.U_tmp,
                       q.f_traj, q.counter, (float*)q.ws, ws_gs(q.ws, q.N, gq)};
   }
-  BatchDesc* dd = nullptr;
-  hipError_t e = hipMalloc((void**)&dd, sizeof(BatchDesc) * (size_t)P);
-  if (e != hipSuccess) { free(hd); DRSA_HIP(e); }
-  int rc = DRSA_OK;
-  auto ok = [&](hipError_t err, const char* what) -> bool {
-    if (err == hipSuccess) return true;
-    drsa::set_error("drsa_run_batched: %s: %s", what, hipGetErrorString(err));
-    rc = (int)err;
-    return false;
-  };
-  if (!ok(hipMemcpyAsync(dd, hd, sizeof(BatchDesc) * (size_t)P, hipMemcpyHostToDevice, s), "copy")) goto done;
-  for (int p = 0; p < P && !rc; ++p) ok(hipMemsetAsync(probs[p].counter, 0, sizeof(int), s), "memset");
-  if (rc) goto done;
-  {
-    // launchers for the geometry
-    auto launch_phase = [&](int parity, int final_obj) -> int {
-      auto part = [&](auto dpt, auto dkt) -> int {
-        constexpr int DP = decltype(dpt)::value, DKP = decltype(dkt)::value;
+  // descriptor table on the device; freed once the stream has drained (the kernels read it)
+  struct DeviceTable {
+    hipStream_t s;
+    BatchDesc* ptr = nullptr;
+    ~DeviceTable() {
+      if (!ptr) return;
+      (void)hipStreamSynchronize(s);
+      (void)hipFree(ptr);
+    }
+  } table{s};
+  DRSA_HIP(hipMalloc((void**)&table.ptr, sizeof(BatchDesc) * (size_t)P));
+  const BatchDesc* dd = table.ptr;
+  DRSA_HIP(hipMemcpyAsync(table.ptr, hd.data(), sizeof(BatchDesc) * (size_t)P, hipMemcpyHostToDevice, s));
+  for (int p = 0; p < P; ++p) DRSA_HIP(hipMemsetAsync(probs[p].counter, 0, sizeof(int), s));
+  // one step (or, with final_obj, the objective alone) of every problem: partial, reduce, finish
+  auto launch_phase = [&](int parity, int final_obj) -> int {
+    int r = with_dp(g.DP, [&](auto dp) -> int {
+      constexpr int DP = decltype(dp)::value;
+      return with_dkp<DP>(g.DKp, [&](auto dkp) -> int {
+        constexpr int DKP = decltype(dkp)::value;
         using Cfg = PCfg<DP, DKP>;
         if constexpr (DKP >= 64) {     // = leafwise
           auto kern = vec ? drsa_partial_leaf_batched_kernel<DP, DKP, true> : drsa_partial_leaf_batched_kernel<DP, DKP, false>;
@@ -2015,107 +2004,54 @@ int drsa_amd_drsa_run_batched(int P, const drsa_amd_problem_t* probs, int steps,
         }
         DRSA_LAUNCH_CHECK();
         return DRSA_OK;
-      };
-      int r = DRSA_EUNSUPPORTED;
-      using I = std::integral_constant<int, 1>;
-      (void)sizeof(I);
-#define PB_DK(DPV)                                                                                            \
-  switch (g.DKp) {                                                                                            \
-    case 1: r = part(std::integral_constant<int, DPV>{}, std::integral_constant<int, 1>{}); break;            \
-    case 2: r = part(std::integral_constant<int, DPV>{}, std::integral_constant<int, 2>{}); break;            \
-    case 4: r = part(std::integral_constant<int, DPV>{}, std::integral_constant<int, 4>{}); break;            \
-    case 8: r = part(std::integral_constant<int, DPV>{}, std::integral_constant<int, 8>{}); break;            \
-    case 16: r = part(std::integral_constant<int, DPV>{}, std::integral_constant<int, 16>{}); break;          \
-    case 32: if constexpr (DPV >= 32) r = part(std::integral_constant<int, DPV>{}, std::integral_constant<int, (DPV >= 32 ? 32 : 1)>{}); break; \
-    case 64: if constexpr (DPV >= 64) r = part(std::integral_constant<int, DPV>{}, std::integral_constant<int, (DPV >= 64 ? 64 : 1)>{}); break; \
-    default: break;                                                                                           \
-  }
-      switch (g.DP) {
-        case 16: PB_DK(16) break;
-        case 32: PB_DK(32) break;
-        case 64: PB_DK(64) break;
-        case 128: PB_DK(128) break;
-      }
-#undef PB_DK
-      if (r) return r;
-      hipLaunchKernelGGL(drsa_reduce_batched_kernel, dim3((unsigned)((E + 63) / 64), P), dim3(256), 0, s, dd,
-                         (int)E, (int)ES);
+      });
+    });
+    if (r) return r;
+    hipLaunchKernelGGL(drsa_reduce_batched_kernel, dim3((unsigned)((E + 63) / 64), P), dim3(256), 0, s, dd,
+                       (int)E, (int)ES);
+    DRSA_LAUNCH_CHECK();
+    return with_dp(g.DP, [&](auto dp) -> int {
+      constexpr int DP = decltype(dp)::value;
+      const size_t lds = finish_lds<DP>();
+      DRSA_SMEM(drsa_finish_batched_kernel<DP>, lds);
+      hipLaunchKernelGGL(drsa_finish_batched_kernel<DP>, dim3(P), dim3(fin_threads<polar_dim<DP>()>()), lds, s, dd,
+                         parity, final_obj ? 1 : 0, kPolarTol, kPolarMaxIter);
       DRSA_LAUNCH_CHECK();
-      auto fin = [&](auto dpt) -> int {
-        constexpr int DP = decltype(dpt)::value;
-        const size_t lds = finish_lds<DP>();
-        DRSA_SMEM(drsa_finish_batched_kernel<DP>, lds);
-        hipLaunchKernelGGL(drsa_finish_batched_kernel<DP>, dim3(P), dim3(fin_threads<polar_dim<DP>()>()), lds, s, dd,
-                           parity, final_obj ? 1 : 0, kPolarTol, kPolarMaxIter);
-        DRSA_LAUNCH_CHECK();
-        return DRSA_OK;
-      };
-      switch (g.DP) {
-        case 16: return fin(std::integral_constant<int, 16>{});
-        case 32: return fin(std::integral_constant<int, 32>{});
-        case 64: return fin(std::integral_constant<int, 64>{});
-        default: return fin(std::integral_constant<int, 128>{});
-      }
-    };
-    int done_steps = 0;
-    if (use_graph && steps >= 2 && s) {
-      hipGraph_t graph = nullptr;
-      hipGraphExec_t exec = nullptr;
-      if (!ok(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal), "capture")) goto done;
-      int r1 = launch_phase(0, 0);
-      int r2 = r1 ? r1 : launch_phase(1, 0);
-      hipError_t ce = hipStreamEndCapture(s, &graph);
-      if (r2) { if (graph) (void)hipGraphDestroy(graph); rc = r2; goto done; }
-      if (!ok(ce, "end capture") || !ok(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0), "instantiate")) {
-        if (graph) (void)hipGraphDestroy(graph);
-        goto done;
-      }
-      for (; done_steps + 2 <= steps; done_steps += 2)
-        if (!ok(hipGraphLaunch(exec, s), "graph launch")) break;
-      (void)hipGraphExecDestroy(exec);
-      (void)hipGraphDestroy(graph);
-      if (rc) goto done;
-    }
-    for (; done_steps < steps; ++done_steps) {
-      int r = launch_phase(done_steps & 1, 0);
-      if (r) { rc = r; goto done; }
-    }
-    if (steps & 1) {   // U_S sits in U_tmp: bring it home
-      for (int p = 0; p < P; ++p)
-        if (!ok(hipMemcpyAsync(probs[p].U_io, probs[p].U_tmp, (size_t)probs[p].d * probs[p].d * sizeof(float),
-                               hipMemcpyDeviceToDevice, s), "copy")) goto done;
-    }
-    {
-      int r = launch_phase(0, 1);   // final objective at U_S -> f_traj[steps]
-      if (r) { rc = r; goto done; }
-    }
-  }
-done:
-  (void)hipStreamSynchronize(s);
-  (void)hipFree(dd);
-  free(hd);
-  return rc;
+      return DRSA_OK;
+    });
+  };
+  auto pair = [&]() -> int {
+    int r = launch_phase(0, 0);
+    return r ? r : launch_phase(1, 0);
+  };
+  auto tail = [&]() -> int {   // U_S sits in U_tmp: bring it home
+    if (int r = launch_phase(0, 0)) return r;
+    for (int p = 0; p < P; ++p)
+      DRSA_HIP(hipMemcpyAsync(probs[p].U_io, probs[p].U_tmp, (size_t)probs[p].d * probs[p].d * sizeof(float),
+                              hipMemcpyDeviceToDevice, s));
+    return DRSA_OK;
+  };
+  // use_graph on the null stream runs the eager pairs here (unlike drsa_run / run_multi).
+  // final objective at U_S -> f_traj[steps]; table's destructor synchronises s on every path
+  return run_steps(s, steps, use_graph && s, pair, tail, [&] { return launch_phase(0, 1); });
 }
 
 int drsa_amd_polar(const float* V, int d, float* U_out, int* iters_out, void* stream) {
   DRSA_REQUIRE(d >= 1 && d <= 128, "polar: unsupported d=%d (1..128)", d);
   DRSA_REQUIRE(V && U_out, "polar: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  auto go = [&](auto tag) -> int {
-    constexpr int DP = decltype(tag)::value;
-    const size_t lds = finish_lds<DP>();
-    DRSA_SMEM(polar_kernel<DP>, lds);
-    hipLaunchKernelGGL(polar_kernel<DP>, dim3(1), dim3(fin_threads<DP>()), lds, s, V, d, U_out, kPolarTol,
-                       kPolarMaxIter, iters_out);
-    DRSA_LAUNCH_CHECK();
-    return DRSA_OK;
-  };
-  const int DP = pow2ceil(d < 32 ? 32 : d);
-  switch (DP) {
-    case 32: return go(std::integral_constant<int, 32>{});
-    case 64: return go(std::integral_constant<int, 64>{});
-    default: return go(std::integral_constant<int, 128>{});
-  }
+  return with_dp(pow2ceil(d < 32 ? 32 : d), [&](auto dp) -> int {
+    constexpr int DP = decltype(dp)::value;
+    if constexpr (DP >= 32) {   // the polar alone pads to 32 at least
+      const size_t lds = finish_lds<DP>();
+      DRSA_SMEM(polar_kernel<DP>, lds);
+      hipLaunchKernelGGL(polar_kernel<DP>, dim3(1), dim3(fin_threads<DP>()), lds, s, V, d, U_out, kPolarTol,
+                         kPolarMaxIter, iters_out);
+      DRSA_LAUNCH_CHECK();
+      return DRSA_OK;
+    }
+    return DRSA_EUNSUPPORTED;
+  });
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@ Public names and argument meanings follow the reference:
 """
 from __future__ import annotations
 
+import ctypes
 import os
 import pickle
 from typing import Callable, List, Optional
@@ -76,7 +77,6 @@ class DrsaWorkspace:
         """1 if the cooperative finish of the last run on this workspace timed out (U, f NaN from
         that step on), else 0.  drsa_run raises on it by itself; this is for a run the caller
         captured into its own graph (drsa_amd_drsa_coop_status; synchronises the stream)."""
-        import ctypes
         st = ctypes.c_int(0)
         _capi.call("drsa_amd_drsa_coop_status", self.ptr, self.N, self.d, self.K, ctypes.addressof(st),
                    _capi.stream_ptr(self.buf.device))
@@ -139,22 +139,19 @@ def drsa_run(A, C, U0, K: int, steps: int, ws: Optional[DrsaWorkspace] = None,
     return U, traj
 
 
-def drsa_run_joint(problems, steps: int, use_graph: bool = True):
-    """Several independent DRSA problems advanced together (C5: the same model's layers j=26 and
-    j=33, K=16 each; the reference optimises them one after another, optsubspaces.py:18-23).
-
-    ``problems``: list of (A, C, U0, K) on one device; A, C fp32, or bf16 / fp16 (C5: the
-    U-projection GEMM then runs on bf16 / fp16 MFMA with fp32 accumulation).  One hipGraph holds every problem's step
-    on its own forked stream (drsa_amd_drsa_run_multi).  Returns [(U_S, trajectory [S+1])]."""
-    import ctypes
-    if not problems:
-        return []
+def _pack_problems(problems, steps: int, use_graph: bool, who: str, fp32_only: bool = False):
+    """Shared set-up of drsa_run_joint / drsa_run_batched: checks each (A, C, U0, K), allocates its
+    workspace, U (a copy of U0), U_tmp and trajectory on the first problem's device and packs the
+    drsa_amd_problem_t array.  Returns (array, [(U, traj)], objects that must outlive the call,
+    stream handle, graph flag)."""
     dev = problems[0][0].device
     keep, structs, outs = [], [], []
     for A, C, U0, K in problems:
         _check_problem(A, C, U0, K)
         if A.device != dev:
-            raise ValueError("drsa_run_joint: all problems must live on one device")
+            raise ValueError(f"{who}: all problems must live on one device")
+        if fp32_only and A.dtype != torch.float32:
+            raise ValueError(f"{who}: fp32 problems only (use drsa_run_joint for bf16 / fp16)")
         N, d = A.shape
         ws = DrsaWorkspace(N, d, K, dev)
         U = U0.detach().clone().contiguous()
@@ -166,10 +163,21 @@ def drsa_run_joint(problems, steps: int, use_graph: bool = True):
                                          traj.data_ptr(), ws.counter.data_ptr(), ws.ptr, ws.nbytes,
                                          {torch.bfloat16: 1, torch.float16: 2}.get(A.dtype, 0)))
     arr = (_capi.DrsaProblem * len(structs))(*structs)
-    stream = torch.cuda.current_stream(dev)
-    graph = bool(use_graph) and stream.cuda_stream != 0
-    _capi.call("drsa_amd_drsa_run_multi", len(structs), ctypes.addressof(arr), int(steps), 1 if graph else 0,
-               stream.cuda_stream)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    return arr, outs, keep, stream, 1 if use_graph and stream != 0 else 0
+
+
+def drsa_run_joint(problems, steps: int, use_graph: bool = True):
+    """Several independent DRSA problems advanced together (C5: the same model's layers j=26 and
+    j=33, K=16 each; the reference optimises them one after another, optsubspaces.py:18-23).
+
+    ``problems``: list of (A, C, U0, K) on one device; A, C fp32, or bf16 / fp16 (C5: the
+    U-projection GEMM then runs on bf16 / fp16 MFMA with fp32 accumulation).  One hipGraph holds every problem's step
+    on its own forked stream (drsa_amd_drsa_run_multi).  Returns [(U_S, trajectory [S+1])]."""
+    if not problems:
+        return []
+    arr, outs, _keep, stream, graph = _pack_problems(problems, steps, use_graph, "drsa_run_joint")
+    _capi.call("drsa_amd_drsa_run_multi", len(arr), ctypes.addressof(arr), int(steps), graph, stream)
     return outs
 
 
@@ -188,29 +196,10 @@ def drsa_run_batched(problems, steps: int, blocks: int = 0, use_graph: bool = Tr
     about this many partial workgroups per problem (0 = automatic), each folding whole groups of
     drsa_run's fixed 256-leaf row partition on chip: every result equals drsa_run's bit for bit,
     for any ``blocks``.  Returns [(U_S, trajectory [S+1])]."""
-    import ctypes
     if not problems:
         return []
-    dev = problems[0][0].device
-    keep, structs, outs = [], [], []
-    for A, C, U0, K in problems:
-        _check_problem(A, C, U0, K)
-        if A.dtype != torch.float32:
-            raise ValueError("drsa_run_batched: fp32 problems only (use drsa_run_joint for bf16 / fp16)")
-        N, d = A.shape
-        ws = DrsaWorkspace(N, d, K, dev)
-        U = U0.detach().clone().contiguous()
-        U_tmp = torch.empty_like(U)
-        traj = torch.empty(steps + 1, dtype=torch.float32, device=dev)
-        keep += [ws, U_tmp, A, C]
-        outs.append((U, traj))
-        structs.append(_capi.DrsaProblem(A.data_ptr(), C.data_ptr(), N, d, int(K), U.data_ptr(), U_tmp.data_ptr(),
-                                         traj.data_ptr(), ws.counter.data_ptr(), ws.ptr, ws.nbytes, 0))
-    arr = (_capi.DrsaProblem * len(structs))(*structs)
-    stream = torch.cuda.current_stream(dev)
-    graph = bool(use_graph) and stream.cuda_stream != 0
-    _capi.call("drsa_amd_drsa_run_batched", len(structs), ctypes.addressof(arr), int(steps), int(blocks),
-               1 if graph else 0, stream.cuda_stream)
+    arr, outs, _keep, stream, graph = _pack_problems(problems, steps, use_graph, "drsa_run_batched", fp32_only=True)
+    _capi.call("drsa_amd_drsa_run_batched", len(arr), ctypes.addressof(arr), int(steps), int(blocks), graph, stream)
     return outs
 
 
