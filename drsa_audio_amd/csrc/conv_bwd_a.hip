@@ -15,21 +15,17 @@
 #endif
 
 #define CONV_FAMILY_BWD64(CIN, NG, AM, C8)                                              \
-  CONV_ENTRY(CIN, 64, 8, 16, 8, DRSA_CONV_CIC_BWD64, NG, AM, drsa_conv::EPI_BWD),       \
-  CONV_ENTRY(CIN, 64, 8, 8, 4, C8, NG, AM, drsa_conv::EPI_BWD)
+  CONV_ENTRY(CIN, 64, 8, 16, 8, DRSA_CONV_CIC_BWD64, NG, AM, drsa_conv::EPI_BWD, 0, 2), \
+  CONV_ENTRY(CIN, 64, 8, 8, 4, C8, NG, AM, drsa_conv::EPI_BWD, 0, 2)
 // C8: the chunk of the 8 x 8 tile (64 -> 64: 8, 0.212 -> 0.193 ms; 128 -> 64: 16, 0.053 vs 0.057 ms)
-#define BWD_SET64(CIN, C8)                                          \
-  CONV_FAMILY_BWD64(CIN, 1, drsa_conv::A_DENSE, C8),                \
-  CONV_FAMILY_BWD64(CIN, 2, drsa_conv::A_DENSE, C8),                \
-  CONV_FAMILY_BWD64(CIN, 1, drsa_conv::A_POOLSPARSE, C8),           \
+#define BWD_SET64(CIN, C8)                                \
+  CONV_FAMILY_BWD64(CIN, 1, drsa_conv::A_DENSE, C8),      \
+  CONV_FAMILY_BWD64(CIN, 2, drsa_conv::A_DENSE, C8),      \
+  CONV_FAMILY_BWD64(CIN, 1, drsa_conv::A_POOLSPARSE, C8), \
   CONV_FAMILY_BWD64(CIN, 2, drsa_conv::A_POOLSPARSE, C8)
 
-namespace drsa_conv {
-static const Entry kTableBwdA_e[] = {
+CONV_TABLE(kTableBwdA,
     BWD_SET64(128, 16),
     BWD_SET64(64, DRSA_CONV_CIC_BWD64_T8),
     // the (2,4) pool backward folded into the staging (VGGish block 1 at W = 256: 8 x 16 tiles)
-    CONV_ENTRY_P4B(64, 64, 8, 16, 8, DRSA_CONV_CIC_BWD64),
-};
-extern const Table kTableBwdA = {kTableBwdA_e, (int)(sizeof(kTableBwdA_e) / sizeof(kTableBwdA_e[0]))};
-}  // namespace drsa_conv
+    CONV_ENTRY(64, 64, 8, 16, 8, DRSA_CONV_CIC_BWD64, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 0, 4))

@@ -9,13 +9,9 @@
 #define DRSA_CONV_CIC_BWD64_32 8
 #endif
 
-namespace drsa_conv {
-static const Entry kTableBwdB_e[] = {
+CONV_TABLE(kTableBwdB,
     BWD_SET(64, 32, DRSA_CONV_CIC_BWD64_32),
-    BWD_SET(32, 32, DRSA_CONV_CIC_BWD32),
-};
-extern const Table kTableBwdB = {kTableBwdB_e, (int)(sizeof(kTableBwdB_e) / sizeof(kTableBwdB_e[0]))};
-}  // namespace drsa_conv
+    BWD_SET(32, 32, DRSA_CONV_CIC_BWD32))
 
 #ifdef DRSA_CONV_STAMP
 extern "C" int drsa_amd_debug_conv_stamps(void* buf) {

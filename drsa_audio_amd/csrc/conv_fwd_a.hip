@@ -6,10 +6,6 @@
 #define DRSA_CONV_CIC_FWD32 8
 #endif
 
-namespace drsa_conv {
-static const Entry kTableFwdA_e[] = {
+CONV_TABLE(kTableFwdA,
     FWD_SET(1, 32, 1),
-    FWD_SET(32, 32, DRSA_CONV_CIC_FWD32),
-};
-extern const Table kTableFwdA = {kTableFwdA_e, (int)(sizeof(kTableFwdA_e) / sizeof(kTableFwdA_e[0]))};
-}  // namespace drsa_conv
+    FWD_SET(32, 32, DRSA_CONV_CIC_FWD32))

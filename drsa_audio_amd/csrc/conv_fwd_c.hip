@@ -9,10 +9,6 @@
 #define DRSA_CONV_CIC_FWD64_128 4   // 8 x 8 tiles at 3 waves/SIMD (166 VGPRs)
 #endif
 
-namespace drsa_conv {
-static const Entry kTableFwdC_e[] = {
+CONV_TABLE(kTableFwdC,
     FWD_SET(64, 64, DRSA_CONV_CIC_FWD64_64),
-    FWD_SET(64, 128, DRSA_CONV_CIC_FWD64_128),
-};
-extern const Table kTableFwdC = {kTableFwdC_e, (int)(sizeof(kTableFwdC_e) / sizeof(kTableFwdC_e[0]))};
-}  // namespace drsa_conv
+    FWD_SET(64, 128, DRSA_CONV_CIC_FWD64_128))

@@ -3,10 +3,6 @@
 // create_model.py:61), fp32 (CIC 8) and bf16 operands.
 #include "lrp_conv_kernel.h"
 
-namespace drsa_conv {
-static const Entry kTableFwdP4_e[] = {
+CONV_TABLE(kTableFwdP4,
     FWD_SET_P4(64, 64, 8, 0),
-    FWD_SET_P4(64, 64, 16, 1),
-};
-extern const Table kTableFwdP4 = {kTableFwdP4_e, (int)(sizeof(kTableFwdP4_e) / sizeof(kTableFwdP4_e[0]))};
-}  // namespace drsa_conv
+    FWD_SET_P4(64, 64, 16, 1))

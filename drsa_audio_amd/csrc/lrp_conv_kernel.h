@@ -1236,95 +1236,66 @@ struct Entry {
   int pw = 2;   // pool window width (ConvCfg PW)
 };
 
-#define CONV_ENTRY(CIN, COUT, TH, TW, MW, CIC, NG, AM, EP)                                                 \
-  drsa_conv::Entry{CIN, COUT, TH, TW, MW, CIC, NG, AM, EP,                                                 \
-                   drsa_conv::conv3x3_kernel<CIN, COUT, TH, TW, MW, CIC, NG, AM, EP>,                      \
-                   drsa_conv::ConvCfg<CIN, COUT, TH, TW, MW, CIC, NG, AM, EP>::lds_floats * sizeof(float)}
-
-// fp32 per-clone backward with g at (2,4)-pool resolution (VGGish block 1, create_model.py:61)
-#define CONV_ENTRY_P4B(CIN, COUT, TH, TW, MW, CIC)                                                          \
-  drsa_conv::Entry{CIN, COUT, TH, TW, MW, CIC, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD,              \
-                   drsa_conv::conv3x3_kernel<CIN, COUT, TH, TW, MW, CIC, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 0, 4>, \
-                   drsa_conv::ConvCfg<CIN, COUT, TH, TW, MW, CIC, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 0, 4>::lds_floats * sizeof(float), 0, 4}
-
-#define CONV_ENTRY_BFA(CIN, COUT, TH, TW, MW, NG, AM, EP)                                                 \
-  drsa_conv::Entry{CIN, COUT, TH, TW, MW, 16, NG, AM, EP,                                                 \
-                   drsa_conv::conv3x3_kernel<CIN, COUT, TH, TW, MW, 16, NG, AM, EP, 1>,                   \
-                   drsa_conv::ConvCfg<CIN, COUT, TH, TW, MW, 16, NG, AM, EP, 1>::lds_floats * sizeof(float), 1}
-// bf16-operand per-clone backward (ET = 1), dense and pool-sparse g, one weight set
-#define BWD_SET_BF(CIN, COUT)                                                                    \
-  CONV_ENTRY_BFA(CIN, COUT, 8, 32, 8, 1, drsa_conv::A_DENSE, drsa_conv::EPI_BWD),                \
-  CONV_ENTRY_BFA(CIN, COUT, 8, 16, 8, 1, drsa_conv::A_DENSE, drsa_conv::EPI_BWD),                \
-  CONV_ENTRY_BFA(CIN, COUT, 8, 8, 4, 1, drsa_conv::A_DENSE, drsa_conv::EPI_BWD),                 \
-  CONV_ENTRY_BFA(CIN, COUT, 8, 32, 8, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD),           \
-  CONV_ENTRY_BFA(CIN, COUT, 8, 16, 8, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD),           \
-  CONV_ENTRY_BFA(CIN, COUT, 8, 8, 4, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD)
-
-// bf16-operand per-clone backward with g at (2,4)-pool resolution (VGGish block 1)
-#define CONV_ENTRY_BFA_P4(CIN, COUT, TH, TW, MW)                                                           \
-  drsa_conv::Entry{CIN, COUT, TH, TW, MW, 16, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD,              \
-                   drsa_conv::conv3x3_kernel<CIN, COUT, TH, TW, MW, 16, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 1, 4>, \
-                   drsa_conv::ConvCfg<CIN, COUT, TH, TW, MW, 16, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 1, 4>::lds_floats * sizeof(float), 1, 4}
-#define BWD_SET_BF_P4(CIN, COUT)                       \
-  CONV_ENTRY_BFA_P4(CIN, COUT, 8, 32, 8),              \
-  CONV_ENTRY_BFA_P4(CIN, COUT, 8, 16, 8),              \
-  CONV_ENTRY_BFA_P4(CIN, COUT, 8, 8, 4)
-
-#define CONV_ENTRY_BF(CIN, COUT, TH, TW, MW, NG, EP)                                                     \
-  drsa_conv::Entry{CIN, COUT, TH, TW, MW, 16, NG, drsa_conv::A_DENSE, EP,                                 \
-                   drsa_conv::conv3x3_kernel<CIN, COUT, TH, TW, MW, 16, NG, drsa_conv::A_DENSE, EP, 1>,   \
-                   drsa_conv::ConvCfg<CIN, COUT, TH, TW, MW, 16, NG, drsa_conv::A_DENSE, EP, 1>::lds_floats * sizeof(float), 1}
-
-// 2x4-pool forward (VGGish block 1, create_model.py:61): fp32 and bf16 operands
-#define CONV_ENTRY_P4(CIN, COUT, TH, TW, MW, CIC, NG, ET)                                                  \
-  drsa_conv::Entry{CIN, COUT, TH, TW, MW, CIC, NG, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL,           \
-                   drsa_conv::conv3x3_kernel<CIN, COUT, TH, TW, MW, CIC, NG, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 4>, \
-                   drsa_conv::ConvCfg<CIN, COUT, TH, TW, MW, CIC, NG, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 4>::lds_floats * sizeof(float), ET, 4}
-#define CONV_FAMILY_P4(CIN, COUT, CIC, NG, ET)                    \
-  CONV_ENTRY_P4(CIN, COUT, 8, 32, 8, CIC, NG, ET),                 \
-  CONV_ENTRY_P4(CIN, COUT, 8, 16, 8, CIC, NG, ET),                 \
-  CONV_ENTRY_P4(CIN, COUT, 8, 8, 4, CIC, NG, ET)
-#define FWD_SET_P4(CIN, COUT, CIC, ET)                                                  \
-  CONV_FAMILY_P4(CIN, COUT, CIC, 1, ET), CONV_FAMILY_P4(CIN, COUT, CIC, 2, ET), CONV_FAMILY_P4(CIN, COUT, CIC, 3, ET)
-
-// tile families (the choice: lrp_conv.hip find): 8x32 / 8x16 (MW 8), 8x8 (MW 4)
-#define CONV_FAMILY(CIN, COUT, CIC, NG, AM, EP)                      \
-  CONV_ENTRY(CIN, COUT, 8, 32, 8, CIC, NG, AM, EP),                  \
-  CONV_ENTRY(CIN, COUT, 8, 16, 8, CIC, NG, AM, EP),                  \
-  CONV_ENTRY(CIN, COUT, 8, 8, 4, CIC, NG, AM, EP)
-
-#define FWD_SET(CIN, COUT, CIC)                                                        \
-  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL),          \
-  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL),          \
-  CONV_FAMILY(CIN, COUT, CIC, 3, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL),          \
-  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_RELU),          \
-  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_RELU),          \
-  CONV_FAMILY(CIN, COUT, CIC, 3, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_RELU)
-
-#define BWD_SET(CIN, COUT, CIC)                                                        \
-  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_DENSE, drsa_conv::EPI_BWD),               \
-  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_DENSE, drsa_conv::EPI_BWD),               \
-  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD),          \
-  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD)
-
-#define CONV_FAMILY_BF(CIN, COUT, NG, EP)                      \
-  CONV_ENTRY_BF(CIN, COUT, 8, 32, 8, NG, EP),                  \
-  CONV_ENTRY_BF(CIN, COUT, 8, 16, 8, NG, EP),                  \
-  CONV_ENTRY_BF(CIN, COUT, 8, 8, 4, NG, EP)
-
-// bf16-operand forward (ET = 1), every denominator set count and both epilogues
-#define FWD_SET_BF(CIN, COUT)                                                 \
-  CONV_FAMILY_BF(CIN, COUT, 1, drsa_conv::EPI_FWD_POOL),                      \
-  CONV_FAMILY_BF(CIN, COUT, 2, drsa_conv::EPI_FWD_POOL),                      \
-  CONV_FAMILY_BF(CIN, COUT, 3, drsa_conv::EPI_FWD_POOL),                      \
-  CONV_FAMILY_BF(CIN, COUT, 1, drsa_conv::EPI_FWD_RELU),                      \
-  CONV_FAMILY_BF(CIN, COUT, 2, drsa_conv::EPI_FWD_RELU),                      \
-  CONV_FAMILY_BF(CIN, COUT, 3, drsa_conv::EPI_FWD_RELU)
-
 struct Table {
   const Entry* entries;
   int n;
 };
 
+// One table entry from the eleven template arguments of ConvCfg / conv3x3_kernel, in their order:
+// CIN, COUT, TH, TW, MW, CIC, NG, AMODE, EPI, ET, PW
+template <int... P>
+constexpr Entry conv_entry() {
+  static_assert(sizeof...(P) == 11, "CONV_ENTRY takes every ConvCfg parameter");
+  constexpr int p[] = {P...};
+  return Entry{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8],
+               conv3x3_kernel<P...>, ConvCfg<P...>::lds_floats * sizeof(float), p[9], p[10]};
+}
+#define CONV_ENTRY(CIN, COUT, TH, TW, MW, CIC, NG, AM, EP, ET, PW) \
+  drsa_conv::conv_entry<CIN, COUT, TH, TW, MW, CIC, NG, AM, EP, ET, PW>()
+
+// tile family (the choice: lrp_conv.hip find): 8x32 / 8x16 (MW 8), 8x8 (MW 4)
+#define CONV_FAMILY(CIN, COUT, CIC, NG, AM, EP, ET, PW)       \
+  CONV_ENTRY(CIN, COUT, 8, 32, 8, CIC, NG, AM, EP, ET, PW),   \
+  CONV_ENTRY(CIN, COUT, 8, 16, 8, CIC, NG, AM, EP, ET, PW),   \
+  CONV_ENTRY(CIN, COUT, 8, 8, 4, CIC, NG, AM, EP, ET, PW)
+
+// forward: every denominator set count and both epilogues (2x2 pool, ReLU only)
+#define FWD_SET_ET(CIN, COUT, CIC, ET)                                                      \
+  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 2),        \
+  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 2),        \
+  CONV_FAMILY(CIN, COUT, CIC, 3, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 2),        \
+  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_RELU, ET, 2),        \
+  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_RELU, ET, 2),        \
+  CONV_FAMILY(CIN, COUT, CIC, 3, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_RELU, ET, 2)
+#define FWD_SET(CIN, COUT, CIC) FWD_SET_ET(CIN, COUT, CIC, 0)
+// bf16-operand forward (ET = 1, 16-channel chunks)
+#define FWD_SET_BF(CIN, COUT) FWD_SET_ET(CIN, COUT, 16, 1)
+
+// 2x4-pool forward (VGGish block 1, create_model.py:61): fp32 and bf16 operands
+#define FWD_SET_P4(CIN, COUT, CIC, ET)                                                      \
+  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 4),        \
+  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 4),        \
+  CONV_FAMILY(CIN, COUT, CIC, 3, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 4)
+
+// fp32 per-clone backward: one or two weight sets, dense and 2x2-pool-sparse g
+#define BWD_SET(CIN, COUT, CIC)                                                             \
+  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_DENSE, drsa_conv::EPI_BWD, 0, 2),              \
+  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_DENSE, drsa_conv::EPI_BWD, 0, 2),              \
+  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 0, 2),         \
+  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 0, 2)
+
+// bf16-operand per-clone backward (ET = 1), dense and pool-sparse g, one weight set
+#define BWD_SET_BF(CIN, COUT)                                                               \
+  CONV_FAMILY(CIN, COUT, 16, 1, drsa_conv::A_DENSE, drsa_conv::EPI_BWD, 1, 2),               \
+  CONV_FAMILY(CIN, COUT, 16, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 1, 2)
+// bf16-operand per-clone backward with g at (2,4)-pool resolution (VGGish block 1)
+#define BWD_SET_BF_P4(CIN, COUT) CONV_FAMILY(CIN, COUT, 16, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 1, 4)
+
+// A conv_*.hip file's entries and its table (listed in lrp_conv.hip's DRSA_CONV_TABLES)
+#define CONV_TABLE(NAME, ...)                                                                     \
+  namespace drsa_conv {                                                                           \
+  static const Entry NAME##_e[] = {__VA_ARGS__};                                                  \
+  extern const Table NAME = {NAME##_e, (int)(sizeof(NAME##_e) / sizeof(NAME##_e[0]))};            \
+  }
 
 }  // namespace drsa_conv

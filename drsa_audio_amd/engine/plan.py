@@ -481,6 +481,36 @@ class LRPEngine:
         self._call(tag, name, cur.data_ptr(), wts.data_ptr(), bias3.data_ptr(), _capi.ptr(den_map), out.data_ptr(),
                    _capi.ptr(amax), _capi.ptr(den), B, st.cin, st.cout, h, w, ng, pool, s)
 
+    def _conv_bwd(self, st: ConvStage, g, amax_in, pool_w, post_den_eps, x_in, out, Bq, clones, h, w, s):
+        """One conv rule-backward launch, the mirror of _conv_fwd.  The entry point follows the post
+        step of the layer below (compact den ring, shared den map, else any other) and the pool width
+        of a pool-sparse g (``amax_in``); it runs on the bf16 weights where the plan prepared them and
+        a kernel exists."""
+        post, den, eps = post_den_eps
+        lib = _capi.lib()
+        # for g at 2x2-pool resolution, has_kernel_bf16_pw(pool_w = 2) is has_kernel_bf16(ng = 1, sparse = 1)
+        bf = st.wts_bwd_bf is not None and bool(
+            lib.drsa_amd_conv_bwd_has_kernel_bf16_pw(st.cout, st.cin, w, pool_w) if amax_in is not None
+            else lib.drsa_amd_conv_bwd_has_kernel_bf16(st.cout, st.cin, w, 1, 0))
+        wts = (st.wts_bwd_bf if bf else st.wts_bwd).data_ptr()
+        x = x_in.data_ptr() if (st.xmode_bwd != XM_NONE or post != POST_NONE) else None
+        tag, shape = f"conv_bwd:{st.name}", (Bq, clones, st.cout, st.cin, h, w)
+        if post == POST_DIV_RING:
+            self._call(tag, "drsa_amd_conv_bwd_den_ring", g.data_ptr(), _capi.ptr(amax_in), wts, int(bf), x,
+                       den["den"].data_ptr(), den["den_const4"].data_ptr(), out.data_ptr(), *shape, st.ng_bwd,
+                       st.xmode_bwd, float(eps), s)
+        elif post == POST_DIV_MAP:
+            self._call(tag, "drsa_amd_conv_bwd_den_map", g.data_ptr(), _capi.ptr(amax_in), pool_w, wts, int(bf), x,
+                       den.data_ptr(), out.data_ptr(), *shape, st.ng_bwd, st.xmode_bwd, float(eps), s)
+        elif pool_w == 4:
+            if not bf:      # backward() folds a (2,4) pool without the den map only onto the bf16 kernel
+                raise EngineError(f"engine: no fp32 backward takes g of {st.name} at (2,4)-pool resolution")
+            self._call(tag, "drsa_amd_conv_bwd_bf16_pw", g.data_ptr(), amax_in.data_ptr(), pool_w, wts, x,
+                       _capi.ptr(den), out.data_ptr(), *shape, st.xmode_bwd, post, float(eps), s)
+        else:
+            self._call(tag, "drsa_amd_conv_bwd_bf16" if bf else "drsa_amd_conv_bwd", g.data_ptr(), _capi.ptr(amax_in),
+                       wts, x, _capi.ptr(den), out.data_ptr(), *shape, st.ng_bwd, st.xmode_bwd, post, float(eps), s)
+
     # ---------------------------------------------------------------- buffers
     def _buf(self, key, shape, dtype=torch.float32):
         t = self._cur_bufs.get(key)
@@ -751,39 +781,9 @@ class LRPEngine:
                 self._call(f"ab_combine:{st.name}", "drsa_amd_ab_combine", pos.data_ptr(), neg.data_ptr(), st.alpha,
                            st.beta, x_in.data_ptr() if post != POST_NONE else None, _capi.ptr(den), out.data_ptr(), Bq,
                            clones, st.cin * h * w, post, float(eps), s)
-            elif post == POST_DIV_RING:
-                out = self._buf((li, "R"), (Bq, st.cin, h, w))
-                bf = st.wts_bwd_bf is not None and _capi.lib().drsa_amd_conv_bwd_has_kernel_bf16(
-                    st.cout, st.cin, w, 1, int(amax_in is not None))
-                self._call(f"conv_bwd:{st.name}", "drsa_amd_conv_bwd_den_ring", g.data_ptr(), _capi.ptr(amax_in),
-                           (st.wts_bwd_bf if bf else st.wts_bwd).data_ptr(), 1 if bf else 0, x_in.data_ptr(),
-                           den["den"].data_ptr(), den["den_const4"].data_ptr(), out.data_ptr(), Bq, clones, st.cout,
-                           st.cin, h, w, st.ng_bwd, st.xmode_bwd, float(eps), s)
-            elif post == POST_DIV_MAP:
-                out = self._buf((li, "R"), (Bq, st.cin, h, w))
-                bf = st.wts_bwd_bf is not None and (
-                    _capi.lib().drsa_amd_conv_bwd_has_kernel_bf16_pw(st.cout, st.cin, w, pool_w) if amax_in is not None
-                    else _capi.lib().drsa_amd_conv_bwd_has_kernel_bf16(st.cout, st.cin, w, 1, 0))
-                self._call(f"conv_bwd:{st.name}", "drsa_amd_conv_bwd_den_map", g.data_ptr(), _capi.ptr(amax_in), pool_w,
-                           (st.wts_bwd_bf if bf else st.wts_bwd).data_ptr(), 1 if bf else 0, x_in.data_ptr(),
-                           den.data_ptr(), out.data_ptr(), Bq, clones, st.cout, st.cin, h, w, st.ng_bwd,
-                           st.xmode_bwd, float(eps), s)
-            elif pool_w == 4:
-                out = self._buf((li, "R"), (Bq, st.cin, h, w))
-                self._call(f"conv_bwd:{st.name}", "drsa_amd_conv_bwd_bf16_pw", g.data_ptr(), amax_in.data_ptr(), 4,
-                           st.wts_bwd_bf.data_ptr(),
-                           x_in.data_ptr() if (st.xmode_bwd != XM_NONE or post != POST_NONE) else None,
-                           _capi.ptr(den), out.data_ptr(), Bq, clones, st.cout, st.cin, h, w, st.xmode_bwd, post,
-                           float(eps), s)
             else:
                 out = self._buf((li, "R"), (Bq, st.cin, h, w))
-                bf = st.wts_bwd_bf is not None and _capi.lib().drsa_amd_conv_bwd_has_kernel_bf16(
-                    st.cout, st.cin, w, 1, int(amax_in is not None))
-                self._call(f"conv_bwd:{st.name}", "drsa_amd_conv_bwd_bf16" if bf else "drsa_amd_conv_bwd", g.data_ptr(),
-                           _capi.ptr(amax_in), (st.wts_bwd_bf if bf else st.wts_bwd).data_ptr(),
-                           x_in.data_ptr() if (st.xmode_bwd != XM_NONE or post != POST_NONE) else None,
-                           _capi.ptr(den), out.data_ptr(), Bq, clones, st.cout, st.cin, h, w, st.ng_bwd,
-                           st.xmode_bwd, post, float(eps), s)
+                self._conv_bwd(st, g, amax_in, pool_w, (post, den, eps), x_in, out, Bq, clones, h, w, s)
             g = out
         return g
 

@@ -171,13 +171,13 @@ int drsa_amd_conv_fwd(const float* in, const float* wts, const float* bias, cons
  * denominators) and every output is fp32, exactly as drsa_amd_conv_fwd.  cin > 1 only (the
  * Cin = 1 first layer stays on the fp32 kernel). */
 size_t drsa_amd_conv_weight_bf16_elems(int cin, int cout, int ng);
+int drsa_amd_conv_fwd_bf16(const float* in, const uint16_t* wts, const float* bias, const float* den_map, float* out,
+                           uint8_t* out_amax, float* out_den, int B, int cin, int cout, int H, int W, int ng,
+                           int pool, void* stream);
 
 /* 1 if drsa_amd_conv_fwd (bf16 = 0) / drsa_amd_conv_fwd_bf16 (bf16 = 1) has a kernel for this
  * shape and pool mode, else 0 (callers then pool with drsa_amd_maxpool_capture). */
 int drsa_amd_conv_fwd_has_kernel(int cin, int cout, int W, int ng, int pool, int bf16);
-int drsa_amd_conv_fwd_bf16(const float* in, const uint16_t* wts, const float* bias, const float* den_map, float* out,
-                           uint8_t* out_amax, float* out_den, int B, int cin, int cout, int H, int W, int ng,
-                           int pool, void* stream);
 
 /* Rule backward of one conv as a transposed conv (flipped/transposed weights), with the
  * max-pool/ReLU backward folded into the input (g_amax != NULL: g at pool resolution) and
@@ -201,20 +201,18 @@ int drsa_amd_conv_bwd(const float* g, const uint8_t* g_amax, const float* wts, c
 int drsa_amd_conv_bwd_bf16(const float* g, const uint8_t* g_amax, const uint16_t* wts, const float* x, const float* den,
                            float* out, int Bq, int clones, int cin, int cout, int H, int W, int ng, int xmode,
                            int post, float eps, void* stream);
+/* 1 if drsa_amd_conv_bwd_bf16 has a kernel for this shape (sparse: g at 2x2-pool resolution). */
+int drsa_amd_conv_bwd_has_kernel_bf16(int cin, int cout, int W, int ng, int sparse);
 
 /* drsa_amd_conv_bwd_bf16 with g at 2 x pool_w max-pool resolution (pool_w = 4: the VGGish (2,4)
  * pool of block 1, create_model.py:61; pool_w = 2 is drsa_amd_conv_bwd_bf16 with g_amax): the pool
  * backward is folded into the staging (each halo pixel takes its cell's g where the cell's argmax
  * byte, row * pool_w + col, names it), so no unpooled g is written or read.  ng = 1. */
-int drsa_amd_conv_bwd_has_kernel_bf16_pw(int cin, int cout, int W, int pool_w);
-/* 1 when the fp32 backward (drsa_amd_conv_bwd_den_map with g_amax) has a kernel for g at 2 x pool_w
- * pool resolution: the (2,4) pool backward folded into the fp32 staging (VGGish block 1; 2 x 4 cells
- * expanded to their 8 pixels at the LDS store; needs W / 4 % 4 == 0), bit-identical to the unpool
- * followed by the dense-g backward (the same MFMA operands). */
-int drsa_amd_conv_bwd_has_kernel_pw(int cin, int cout, int W, int ng, int pool_w);
 int drsa_amd_conv_bwd_bf16_pw(const float* g, const uint8_t* g_amax, int pool_w, const uint16_t* wts, const float* x,
                               const float* den, float* out, int Bq, int clones, int cin, int cout, int H, int W,
                               int xmode, int post, float eps, void* stream);
+/* 1 if drsa_amd_conv_bwd_bf16_pw has a kernel for this shape and pool width. */
+int drsa_amd_conv_bwd_has_kernel_bf16_pw(int cin, int cout, int W, int pool_w);
 
 /* The backward conv (fp32 weights: wts_bf16 = 0, ng 1..2, g dense or 2x2-pool-sparse; bf16 weights:
  * wts_bf16 = 1, ng = 1, g dense or 2 x pool_w pool-sparse) with post = POST_DIV whose denominator is
@@ -226,6 +224,11 @@ int drsa_amd_conv_bwd_bf16_pw(const float* g, const uint8_t* g_amax, int pool_w,
 int drsa_amd_conv_bwd_den_map(const float* g, const uint8_t* g_amax, int pool_w, const void* wts, int wts_bf16,
                               const float* x, const float* den_map, float* out, int Bq, int clones, int cin, int cout,
                               int H, int W, int ng, int xmode, float eps, void* stream);
+/* 1 when the fp32 backward (drsa_amd_conv_bwd_den_map with g_amax) has a kernel for g at 2 x pool_w
+ * pool resolution: the (2,4) pool backward folded into the fp32 staging (VGGish block 1; 2 x 4 cells
+ * expanded to their 8 pixels at the LDS store; needs W / 4 % 4 == 0), bit-identical to the unpool
+ * followed by the dense-g backward (the same MFMA operands). */
+int drsa_amd_conv_bwd_has_kernel_pw(int cin, int cout, int W, int ng, int pool_w);
 
 /* WSquare / Flat first layer under a 2x2 max-pool, with its denominator map split for the next
  * backward (zennit WSquare/Flat: den = conv(1; W^2, b^2); constants.py:29 puts
@@ -250,8 +253,6 @@ int drsa_amd_conv_fwd_den_ring(const float* in, const float* wts, const float* b
 int drsa_amd_conv_bwd_den_ring(const float* g, const uint8_t* g_amax, const void* wts, int wts_bf16, const float* x,
                                const float* den_ring, const float* den_const4, float* out, int Bq, int clones, int cin,
                                int cout, int H, int W, int ng, int xmode, float eps, void* stream);
-/* 1 if drsa_amd_conv_bwd_bf16 has a kernel for this shape (sparse: g at 2x2-pool resolution). */
-int drsa_amd_conv_bwd_has_kernel_bf16(int cin, int cout, int W, int ng, int sparse);
 
 /* Dense layer forward: z = x W^T + b [, relu(z)]  (classifier Linear layers). */
 int drsa_amd_linear_fwd(const float* x, const float* W, const float* bias, float* z_out, float* relu_out, int M,

@@ -131,3 +131,112 @@ def test_coop_status_and_spin_budget_argument_errors():
     assert lib.drsa_amd_drsa_coop_status(ctypes.c_void_p(16), 0, 128, 16, ctypes.addressof(st), None) == _capi.DRSA_EINVAL
     assert lib.drsa_amd_debug_coop_spin_budget(-2) == _capi.DRSA_EINVAL
     assert lib.drsa_amd_debug_coop_spin_budget(-1) == 0
+
+
+# ---------------------------------------------------------------------------------------------
+# conv entry points: one row per argument check of csrc/lrp_conv.hip.  Every row starts from a
+# valid call of that entry point (64 -> 64 channels, 8 x 32 map, batch 2; never launched here: only
+# the changed argument differs, and it is rejected before any device work) and names the argument
+# it breaks, the expected code and a substring of the message.
+# ---------------------------------------------------------------------------------------------
+_PTR = {k: 0x10000 * (i + 1) for i, k in enumerate(
+    ("in", "g", "g_amax", "wts", "bias", "x", "den", "den_map", "den_ring", "den_const4", "out", "out_amax", "out_den"))}
+_CONV_ORDER = {
+    "conv_fwd": "in wts bias den_map out out_amax out_den B cin cout H W ng pool stream",
+    "conv_fwd_bf16": "in wts bias den_map out out_amax out_den B cin cout H W ng pool stream",
+    "conv_fwd_den_ring": "in wts bias den_map out out_amax den_ring B cout H W ng stream",
+    "conv_bwd": "g g_amax wts x den out Bq clones cin cout H W ng xmode post eps stream",
+    "conv_bwd_bf16": "g g_amax wts x den out Bq clones cin cout H W ng xmode post eps stream",
+    "conv_bwd_bf16_pw": "g g_amax pool_w wts x den out Bq clones cin cout H W xmode post eps stream",
+    "conv_bwd_den_map": "g g_amax pool_w wts wts_bf16 x den_map out Bq clones cin cout H W ng xmode eps stream",
+    "conv_bwd_den_ring": "g g_amax wts wts_bf16 x den_ring den_const4 out Bq clones cin cout H W ng xmode eps stream",
+}
+_CONV_VALID = dict(_PTR, B=2, Bq=2, clones=1, cin=64, cout=64, H=8, W=32, ng=1, pool=1, pool_w=2, wts_bf16=0,
+                   xmode=1, post=1, eps=1e-6, stream=None)
+_E, _U = _capi.DRSA_EINVAL, _capi.DRSA_EUNSUPPORTED
+_FWDS, _BWDS = ("conv_fwd", "conv_fwd_bf16"), ("conv_bwd", "conv_bwd_bf16", "conv_bwd_bf16_pw", "conv_bwd_den_map",
+                                               "conv_bwd_den_ring")
+_CONV_REJECTIONS = (
+    # forward, fp32 and bf16 weights
+    *[(e, ch, _E, msg) for e in _FWDS for ch, msg in (
+        (dict(B=0), "bad shape"), (dict(H=0), "bad shape"), (dict(W=0), "bad shape"),
+        (dict(ng=0), "ng must be 1..3"), (dict(ng=4), "ng must be 1..3"),
+        (dict(H=7), "H and W must be even (got 7x32)"), (dict(W=31), "H and W must be even (got 8x31)"),
+        (dict(pool=-1), "pool must be 0"), (dict(pool=3), "pool must be 0"),
+        (dict(out_amax=None), "pool needs out_amax"),
+        (dict(pool=0, W=6), "unpooled output needs W % 4 == 0"),
+        (dict(pool=2, W=6), "2x4 pool needs W % 4 == 0 (got W=6)"))],
+    ("conv_fwd_bf16", dict(cin=1), _E, "cin = 1 runs on drsa_amd_conv_fwd"),
+    ("conv_fwd_bf16", dict(wts=_PTR["wts"] + 8), _E, "16-byte aligned"),
+    ("conv_fwd", dict(cin=128, cout=32), _U, "no kernel for cin=128 cout=32 W=32"),
+    ("conv_fwd_bf16", dict(cin=128, cout=32), _U, "no kernel for cin=128 cout=32 W=32"),
+    # the den-ring first-layer forward
+    *[("conv_fwd_den_ring", {k: None}, _E, "null pointer") for k in ("in", "wts", "den_map", "out", "out_amax", "den_ring")],
+    *[("conv_fwd_den_ring", ch, _E, "needs H >= 4 even and W % 16 == 0 (got") for ch in (
+        dict(B=0), dict(H=2), dict(H=7), dict(W=0), dict(W=24))],
+    ("conv_fwd_den_ring", dict(ng=0), _E, "ng must be 1..3"), ("conv_fwd_den_ring", dict(ng=4), _E, "ng must be 1..3"),
+    # every backward
+    *[(e, ch, _E, "bad batch/clones") for e in _BWDS for ch in (dict(Bq=0), dict(clones=0), dict(Bq=3, clones=2))],
+    *[(e, ch, _E, "W % 4 == 0") for e in _BWDS[:4] for ch in (dict(H=7), dict(W=30))],
+    *[(e, ch, _E, "H must be even and W % 4 == 0 (got") for e in ("conv_bwd", "conv_bwd_bf16", "conv_bwd_den_map")
+      for ch in (dict(H=7), dict(W=30))],
+    *[(e, dict(x=None, post=0), _E, "xmode needs x") for e in _BWDS[:3]],
+    *[(e, ch, _E, "POST_DIV needs x and den") for e in _BWDS[:3] for ch in (
+        dict(x=None, xmode=0), dict(den=None), dict(x=None, xmode=0, post=2))],
+    *[(e, dict(cin=32, cout=64), _U, "no kernel for cin=32 cout=64 W=32") for e in _BWDS if e != "conv_bwd_bf16_pw"],
+    # fp32 weights
+    ("conv_bwd", dict(ng=0), _E, "ng must be 1..2"), ("conv_bwd", dict(ng=3), _E, "ng must be 1..2"),
+    # bf16 weights
+    ("conv_bwd_bf16", dict(ng=2), _E, "the Gamma x-/W- term is for the fp32 first layer"),
+    ("conv_bwd_bf16", dict(cin=8), _E, "cin >= 16"), ("conv_bwd_bf16_pw", dict(cin=8), _E, "cin >= 16"),
+    ("conv_bwd_bf16", dict(wts=_PTR["wts"] + 8), _E, "16-byte aligned"),
+    ("conv_bwd_bf16_pw", dict(wts=_PTR["wts"] + 8), _E, "16-byte aligned"),
+    *[(e, dict(wts_bf16=1, **ch), _E, msg) for e in ("conv_bwd_den_map", "conv_bwd_den_ring") for ch, msg in (
+        (dict(ng=2), "bf16 weights need ng == 1"), (dict(cin=8), "cin >= 16"),
+        (dict(wts=_PTR["wts"] + 8), "16-byte align"))],
+    # g at 2 x pool_w resolution
+    *[("conv_bwd_bf16_pw", ch, _E, "needs g_amax and pool_w 2 or 4") for ch in (
+        dict(g_amax=None), dict(pool_w=0), dict(pool_w=3))],
+    ("conv_bwd_bf16_pw", dict(pool_w=4, cin=32, cout=32), _U, "no kernel for cin=32 cout=32 W=32"),
+    # the shared den map
+    ("conv_bwd_den_map", dict(x=None), _E, "needs x and den"), ("conv_bwd_den_map", dict(den_map=None), _E, "needs x and den"),
+    ("conv_bwd_den_map", dict(pool_w=3), _E, "pool_w must be 2 or 4"),
+    ("conv_bwd_den_map", dict(xmode=3), _E, "bad xmode"), ("conv_bwd_den_map", dict(xmode=-1), _E, "bad xmode"),
+    ("conv_bwd_den_map", dict(ng=0), _E, "1..2"), ("conv_bwd_den_map", dict(ng=3), _E, "1..2"),
+    ("conv_bwd_den_map", dict(ng=2, pool_w=4), _E, "ng 1 under a 2x4 pool"),
+    ("conv_bwd_den_map", dict(pool_w=4, W=8), _E, "2x4 pool-sparse g needs W / 4 % 4 == 0 (got W=8)"),
+    # the compact den ring
+    *[("conv_bwd_den_ring", {k: None}, _E, "needs x, den_ring and den_const4") for k in ("x", "den_ring", "den_const4")],
+    *[("conv_bwd_den_ring", ch, _E, "needs pooled H >= 2 and W >= 8, W % 8 == 0 (got") for ch in (
+        dict(H=1), dict(W=4), dict(W=12))],
+    ("conv_bwd_den_ring", dict(xmode=3), _E, "bad xmode"),
+    ("conv_bwd_den_ring", dict(den_const4=_PTR["den_const4"] + 4), _E, "den_const4 must be 16-byte aligned"),
+    ("conv_bwd_den_ring", dict(ng=0), _E, "ng must be 1..2"), ("conv_bwd_den_ring", dict(ng=3), _E, "ng must be 1..2"),
+    # launch: one sample's planes are addressed with 32-bit offsets
+    *[(e, dict(cin=128, cout=128, H=4096, W=4096), _E, "conv: one sample's channels x H x W must stay below 2^31")
+      for e in _FWDS + ("conv_bwd", "conv_bwd_bf16", "conv_bwd_den_map", "conv_bwd_den_ring")],
+    ("conv_fwd_den_ring", dict(cout=128, H=4096, W=4096), _E, "2^31"),
+)
+
+
+def _conv_call(entry, changes):
+    args = dict(_CONV_VALID, **changes)
+    rc = getattr(_capi.lib(), "drsa_amd_" + entry)(*[args[k] for k in _CONV_ORDER[entry].split()])
+    return rc, _capi.lib().drsa_amd_last_error().decode()
+
+
+@pytest.mark.parametrize("entry,changes,code,needle", _CONV_REJECTIONS,
+                         ids=[f"{e}-{'-'.join(f'{k}={v}' for k, v in c.items())}" for e, c, _, _ in _CONV_REJECTIONS])
+def test_conv_entry_points_reject_bad_arguments(entry, changes, code, needle):
+    rc, msg = _conv_call(entry, changes)
+    assert rc == code, (rc, msg)
+    assert needle in msg, msg
+    # the message names its entry point (the 32-bit-offset limit is checked in the shared launch)
+    assert msg.startswith(entry + ":") or needle.startswith("conv:") or "2^31" in needle, msg
+
+
+def test_conv_rejection_table_covers_every_entry_point():
+    """Each launching conv entry point has rows, and all but the den-ring forward (Cin = 1 kernel,
+    no table lookup) have their "no kernel" row."""
+    assert {e for e, *_ in _CONV_REJECTIONS} == set(_CONV_ORDER)
+    assert {e for e, _, c, _ in _CONV_REJECTIONS if c == _U} == set(_CONV_ORDER) - {"conv_fwd_den_ring"}
