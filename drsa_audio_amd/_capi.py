@@ -87,6 +87,13 @@ SIGNATURES = {
     "drsa_amd_logmel_smem_bytes": (_i32, [_i32, _i32, _i32, _i32, _i32]),
     "drsa_amd_logmel": (_i32, [_fp, _i64, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _ip, _ip, _ip,
                                _fp, _i32, _i32, _i32, _f32, _f32, _fp, _vp]),
+    "drsa_amd_stft_mel_phase": (_i32, [_fp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _ip, _ip, _ip,
+                                       _fp, _i32, _i32, _fp, _fp, _vp]),
+    "drsa_amd_heatmap_mask": (_i32, [_fp, _i64, _i32, _i32, _i32, _i32, _i32, _fp, _i32, _fp, _vp]),
+    "drsa_amd_istft_envelope": (_i32, [_fp, _i32, _i32, _i32, _fp]),
+    "drsa_amd_mel_to_audio": (_i32, [_fp, _fp, _fp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp,
+                                     _vp]),
+    "drsa_amd_audio_normalize": (_i32, [_fp, _i64, _i32, _fp, _i64, _i32, _i32, _vp]),
 }
 
 class DrsaProblem(C.Structure):

@@ -16,6 +16,7 @@
 // chunk).
 #include "common.h"
 #include "drsa_amd.h"
+#include "stockham.h"
 
 #include <stdlib.h>
 
@@ -23,7 +24,6 @@ namespace {
 
 constexpr int LM_WAVES = 8;
 constexpr int LM_THREADS = LM_WAVES * 64;
-constexpr int LM_MAX_STAGES = 8;
 
 struct LogmelArgs {
   const float* wav;
@@ -48,89 +48,6 @@ struct LogmelArgs {
   int o_tw, o_ptw, o_win, o_blo, o_bn, o_boff, o_bw, o_samp, o_fft, o_mel, o_red, smem_floats;
   int o_bwt;                 // n_fft = 800 kernel: band weights transposed [LF_NBT][n_mels + 1]
 };
-
-struct cf {
-  float x, y;
-};
-__device__ __forceinline__ cf cadd(cf a, cf b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ cf csub(cf a, cf b) { return {a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ cf cmul(cf a, cf b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ cf cscale(cf a, float s) { return {a.x * s, a.y * s}; }
-__device__ __forceinline__ cf mul_negi(cf a) { return {a.y, -a.x}; }   // -i * a
-
-// Wave-local LDS hand-off: all lanes' LDS writes are visible to the wave's later reads.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// forward DFT butterflies (sign -i), in place on v[0..R)
-__device__ __forceinline__ void bfly2(cf* v) {
-  cf a = v[0], b = v[1];
-  v[0] = cadd(a, b);
-  v[1] = csub(a, b);
-}
-__device__ __forceinline__ void bfly4(cf* v) {
-  cf t0 = cadd(v[0], v[2]), t1 = csub(v[0], v[2]);
-  cf t2 = cadd(v[1], v[3]), t3 = mul_negi(csub(v[1], v[3]));
-  v[0] = cadd(t0, t2);
-  v[2] = csub(t0, t2);
-  v[1] = cadd(t1, t3);
-  v[3] = csub(t1, t3);
-}
-__device__ __forceinline__ void bfly3(cf* v) {
-  const float s = 0.86602540378443864676f;
-  cf sm = cadd(v[1], v[2]);
-  cf y0 = cadd(v[0], sm);
-  cf t = csub(v[0], cscale(sm, 0.5f));
-  cf u = mul_negi(cscale(csub(v[1], v[2]), s));
-  v[0] = y0;
-  v[1] = cadd(t, u);
-  v[2] = csub(t, u);
-}
-__device__ __forceinline__ void bfly5(cf* v) {
-  const float c1 = 0.30901699437494742410f, c2 = -0.80901699437494742410f;
-  const float s1 = 0.95105651629515357212f, s2 = 0.58778525229247312917f;
-  cf b1 = cadd(v[1], v[4]), b2 = cadd(v[2], v[3]);
-  cf d1 = csub(v[1], v[4]), d2 = csub(v[2], v[3]);
-  cf a0 = v[0];
-  cf r1 = cadd(a0, cadd(cscale(b1, c1), cscale(b2, c2)));
-  cf r2 = cadd(a0, cadd(cscale(b1, c2), cscale(b2, c1)));
-  cf q1 = mul_negi(cadd(cscale(d1, s1), cscale(d2, s2)));   // -i (s1 d1 + s2 d2)
-  cf q2 = mul_negi(csub(cscale(d1, s2), cscale(d2, s1)));   // -i (s2 d1 - s1 d2)
-  v[0] = cadd(a0, cadd(b1, b2));
-  v[1] = cadd(r1, q1);
-  v[4] = csub(r1, q1);
-  v[2] = cadd(r2, q2);
-  v[3] = csub(r2, q2);
-}
-
-// One Stockham pass of radix R over M points (Govindaraju et al. 2008 indexing):
-//   v[r] = in[j + r*M/R] * W_M^{r*k*M/(Ns*R)}, k = j % Ns;  out[(j/Ns)*Ns*R + k + r*Ns] = DFT_R(v)[r]
-template <int R>
-__device__ __forceinline__ void stockham_pass(const cf* __restrict__ in, cf* __restrict__ out, const cf* tw, int M,
-                                              int Ns, int lane) {
-  const int MR = M / R;
-  const int tstep = M / (Ns * R);
-  for (int j = lane; j < MR; j += 64) {
-    const int k = j % Ns;
-    cf v[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) v[r] = in[j + r * MR];
-    if (Ns > 1) {
-#pragma unroll
-      for (int r = 1; r < R; ++r) v[r] = cmul(v[r], tw[r * k * tstep]);
-    }
-    if constexpr (R == 2) bfly2(v);
-    if constexpr (R == 3) bfly3(v);
-    if constexpr (R == 4) bfly4(v);
-    if constexpr (R == 5) bfly5(v);
-    const int base = (j / Ns) * Ns * R + k;
-#pragma unroll
-    for (int r = 0; r < R; ++r) out[base + r * Ns] = v[r];
-  }
-}
 
 __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(LogmelArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -592,14 +509,6 @@ __global__ __launch_bounds__(LF_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
 #endif
 }
 
-int factor_radices(int M, int* r) {
-  int n = 0;
-  while (M % 4 == 0 && n < LM_MAX_STAGES) { r[n++] = 4; M /= 4; }
-  while (M % 2 == 0 && n < LM_MAX_STAGES) { r[n++] = 2; M /= 2; }
-  while (M % 3 == 0 && n < LM_MAX_STAGES) { r[n++] = 3; M /= 3; }
-  while (M % 5 == 0 && n < LM_MAX_STAGES) { r[n++] = 5; M /= 5; }
-  return M == 1 ? n : -1;
-}
 
 }  // namespace
 

@@ -61,6 +61,13 @@ def fbank_bands(fb: torch.Tensor):
             torch.tensor(off, dtype=torch.int32), wv.to(torch.float32).contiguous())
 
 
+def mel_pinv(fb: torch.Tensor, rcond: float = 1e-6) -> np.ndarray:
+    """P = pinv(fb^T) [n_freqs, n_mels] in float64: the minimum-norm least-squares inverse of
+    ``mel = fb^T |X|`` (singular values below ``rcond`` x the largest are dropped).  A plan
+    constant of the audio back end (``xai/explain/audiogen.py``), computed once per Loader."""
+    return np.linalg.pinv(fb.to(torch.float64).numpy().T, rcond=rcond)
+
+
 class Loader:
     """cxai/utils/dataloading.py:13-74 (same constructor) on the HIP front end."""
 
@@ -89,12 +96,31 @@ class Loader:
             fb = melscale_fbanks(self.n_fft // 2 + 1, 0.0, float(self.sample_rate // 2), self.n_mels,
                                  self.sample_rate)
             lo, n, off, w = fbank_bands(fb)
+            pinv = torch.from_numpy(mel_pinv(fb)).to(torch.float32)          # [n_freqs, n_mels]
             self._tables[key] = {
                 "window": torch.hann_window(self.n_fft).to(device),
                 "lo": lo.to(device), "n": n.to(device), "off": off.to(device), "w": w.to(device),
                 "nnz": int(w.numel()), "fb": fb,
+                # audio back end: P = pinv(fb^T) and its transpose (the layout drsa_amd_mel_to_audio reads)
+                "pinv": pinv.to(device), "pinv_t": pinv.t().contiguous().to(device),
             }
         return self._tables[key]
+
+    def analyse(self, wav: torch.Tensor, frame0: int = 0, width: Optional[int] = None, power: int = 1,
+                peak_norm: bool = False):
+        """Chunks [n, L] -> (linear mel |X|^power [n, n_mels, width], complex spectrum X
+        [n, width, n_freq]) of STFT frames frame0..frame0+width-1 (``drsa_amd_stft_mel_phase``)."""
+        _capi.require_gpu(wav, "wav", dtype=torch.float32)
+        width = self.width if width is None else width
+        t = self.tables(wav.device)
+        n, L = wav.shape
+        mel = torch.empty(n, self.n_mels, width, device=wav.device)
+        X = torch.empty(n, width, self.n_fft // 2 + 1, 2, device=wav.device)
+        _capi.call("drsa_amd_stft_mel_phase", wav.data_ptr(), n, L, L, self.n_fft, self.hop_length, self.n_mels, width,
+                   frame0, power, t["window"].data_ptr(), t["lo"].data_ptr(), t["n"].data_ptr(), t["off"].data_ptr(),
+                   t["w"].data_ptr(), t["nnz"], 1 if peak_norm else 0, mel.data_ptr(), X.data_ptr(),
+                   _capi.stream_ptr(wav.device))
+        return mel, torch.view_as_complex(X)
 
     # --------------------------------------------------------------- transform
     def _run(self, wav: torch.Tensor, n_songs: int, song_stride: int, chunks: int, hop_chunks: int, L: int,
@@ -110,16 +136,26 @@ class Loader:
 
     def transform_wav(self, wav: torch.Tensor, return_all: bool = False, clamp: bool = True) -> torch.Tensor:
         """dataloading.py:138-176: waveform chunks [..., L] -> log-mel [-1, 1, n_mels, width]
-        (frames 1..width of the centred STFT)."""
-        if return_all:
-            raise NotImplementedError("transform_wav(return_all=True) returns librosa magnitude/phase for plotting "
-                                      "(out of scope: presentation code)")
+        (frames 1..width of the centred STFT).
+
+        ``return_all=True`` (dataloading.py:163-171) returns ``(wav, mag, phase, mel)`` instead: the
+        STFT magnitude and unit phase (librosa ``magphase``: 1 where the magnitude is 0)
+        [..., n_freq, width] and the linear mel [..., n_mels, width] of frames 0..width-1, one
+        frame earlier than the log-mel's (the reference's own offset), as device tensors."""
         wav = wav.detach()
         if wav.dtype != torch.float32:
             wav = wav.to(torch.float32)
         wav = wav.contiguous()
         L = wav.size(-1)
         rows = wav.numel() // L if L else 0
+        if return_all:
+            mel, X = self.analyse(wav.reshape(rows, L), frame0=0, width=self.width, power=1)
+            X = X.transpose(1, 2)                                           # [rows, n_freq, width]
+            mag = X.abs()
+            phase = torch.where(mag > 0, X / mag, torch.ones_like(X))
+            lead = wav.shape[:-1]
+            return (wav, mag.reshape(*lead, *mag.shape[1:]), phase.reshape(*lead, *phase.shape[1:]),
+                    mel.reshape(*lead, *mel.shape[1:]))
         return self._run(wav, rows, L, 1, 0, L, peak_norm=False, clamp=clamp)
 
     def load_songs(self, songs: torch.Tensor, num_chunks: Optional[int] = None, startpoint: float = 0,

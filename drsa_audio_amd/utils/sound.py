@@ -42,3 +42,25 @@ def peak_normalizer(wav: torch.Tensor) -> torch.Tensor:
     """sound.py:67-70: amplitudes scaled into [-1, 1] by the peak along the last axis."""
     wav = torch.as_tensor(wav)
     return wav / torch.abs(wav).max(dim=-1, keepdim=True)[0]
+
+
+def _rms(x: torch.Tensor, dim=None, keepdim: bool = False) -> torch.Tensor:
+    sq = x * x
+    return torch.sqrt(sq.mean() if dim is None else sq.mean(dim=dim, keepdim=keepdim))
+
+
+def rms_normalizer(wav: torch.Tensor, rms_db: float = 0) -> torch.Tensor:
+    """sound.py:47-64: every row brought to the RMS level ``rms_db`` (dB; 0 dB is an RMS of 1)."""
+    wav = torch.as_tensor(wav)
+    target = 10.0 ** (rms_db / 20.0)
+    return wav * (target / _rms(wav, dim=-1, keepdim=True))
+
+
+def adjust_vol(audio1: torch.Tensor, audio2: torch.Tensor) -> torch.Tensor:
+    """sound.py:73-102: audio2 at the loudness of audio1 (RMS over all elements of each):
+    ``clamp(audio2 * |rms(audio1) / rms(audio2)|, -1, 1)`` -- torchaudio ``Vol(gain, "amplitude")``
+    clamps.  ``Mel2Audio.make_audios_batch`` applies the same per audio inside
+    ``drsa_amd_audio_normalize``; this is the stand-alone form."""
+    audio1, audio2 = torch.as_tensor(audio1), torch.as_tensor(audio2)
+    gain = torch.abs(_rms(audio1).to(audio2.device) / _rms(audio2))
+    return torch.clamp(audio2 * gain, -1, 1)

@@ -432,6 +432,49 @@ int drsa_amd_normalize_sumsq(const float* v, int64_t n, void* ws, size_t ws_byte
 int drsa_amd_normalize_scale(const float* v, int64_t n, int d, const double* sums, int nsums, int64_t n_total,
                              float* out, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Concept audio (cxai/xai/explain/audiogen.py, Mel2Audio): heatmaps -> waveforms.  csrc/audiogen.hip.
+ * Shape rules of the transforms: n_fft even, n_fft/2 = 2^a 3^b 5^c, 1 <= hop <= n_fft, power 1 or 2.
+ * ------------------------------------------------------------------------- */
+
+/* Analysis of n_chunks waveforms (chunk i at wav + i*chunk_stride, chunk_len samples): centred,
+ * reflect-padded STFT with `window`, frames frame0..frame0+width-1.
+ *   mel [n_chunks, n_mels, width]        the band-form filterbank (as drsa_amd_logmel) on |X|^power
+ *   X   [n_chunks, width, n_fft/2+1, 2]  the complex spectrum (re, im), frame-major
+ * peak_norm != 0 divides each chunk by its max |x| first (peak_normalizer). */
+int drsa_amd_stft_mel_phase(const float* wav, int64_t n_chunks, int64_t chunk_stride, int chunk_len, int n_fft,
+                            int hop, int n_mels, int width, int frame0, int power, const float* window,
+                            const int* band_lo, const int* band_n, const int* band_off, const float* band_w,
+                            int band_nnz, int peak_norm, float* mel, float* X, void* stream);
+
+/* generate_mask for n_maps maps [H, W]: hp = relu(h); with a rank r >= 0 keep hp where hp > a[r]
+ * (a = the map's sorted hp; r = floor(p/100 (H*W-1)) is "hp > np.percentile(hp, p)"), r = -1 keeps
+ * all; then the separable Gaussian blur with `taps` [k] (k odd) and reflect padding k/2.  Map i
+ * uses rank_first when i % group == 0, else rank_rest.  The map lives in LDS: DRSA_EUNSUPPORTED
+ * when H*W floats and the tables exceed 160 KB. */
+int drsa_amd_heatmap_mask(const float* heatmaps, int64_t n_maps, int H, int W, int group, int rank_first,
+                          int rank_rest, const float* taps, int k, float* mask, void* stream);
+
+/* Host only (no device work): envelope_host[s], s < hop*(width-1), the overlap-added window^2 at
+ * padded position s + n_fft/2 for `width` frames (fp64 sums, rounded once).  DRSA_EINVAL when it
+ * is not above 1e-11 everywhere in that span (torch.istft's check). */
+int drsa_amd_istft_envelope(const float* window_host, int n_fft, int hop, int width, float* envelope_host);
+
+/* For each of n_src sources and its C masks: mag = relu(P (mel * mask))^(1/power) with
+ * pinv_t = P^T [n_mels, n_fft/2+1]; Y = mag * X/|X| (1 where |X| = 0); istft(Y, center=True):
+ * inverse real FFT, * window, overlap-add at hop, / envelope, n_fft/2 samples dropped at each end.
+ *   mask [n_src, C, n_mels, width];  audio [n_src, C, hop*(width-1)].
+ * Every sample has a fixed summation order: an audio is bit-identical in any batch. */
+int drsa_amd_mel_to_audio(const float* mel, const float* X, const float* mask, int64_t n_src, int C, int n_fft,
+                          int hop, int n_mels, int width, int power, const float* window, const float* pinv_t,
+                          const float* envelope, float* audio, void* stream);
+
+/* In place over n_audio rows of len samples: a / max|a| (a silent row becomes NaN, as the
+ * reference), then, when wav != NULL, adjust_vol against the row's source waveform
+ * wav + (row / C) * wav_stride: clamp(a * |rms(wav) / rms(a)|, -1, 1). */
+int drsa_amd_audio_normalize(float* audio, int64_t n_audio, int len, const float* wav, int64_t wav_stride,
+                             int wav_len, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
