@@ -20,25 +20,14 @@
 namespace {
 
 constexpr int kThreads = 256;
-#ifndef DRSA_FIRST_FWD_PK
-#define DRSA_FIRST_FWD_PK 1
-#endif
 typedef float fp2 __attribute__((ext_vector_type(2)));
 
 // DEN: 0 none, 1 input-independent map (WSquare / Flat), 2 computed from the rule's sets,
 //      3 the map of 1 with the per-sample copy on the border ring only (den_ring_only)
 template <int NG, int DEN>
-#ifndef DRSA_FIRST_FWD_RING2
-#define DRSA_FIRST_FWD_RING2 1
-#endif
-#ifndef DRSA_FIRST_FWD_RUNROLL
-#define DRSA_FIRST_FWD_RUNROLL 8   // ring pass: 8 channels of gathers in flight (4: +3 %, 16: +1 %, micro-benchmark)
-#endif
-#ifndef DRSA_FIRST_FWD_WPE
-#define DRSA_FIRST_FWD_WPE 1
-#endif
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(DRSA_FIRST_FWD_WPE))) void first_conv_pool_kernel(ConvArgs a, const float* __restrict__ wts, const float* __restrict__ bias,
-                                                            const float* __restrict__ den_map, int cout_p, int total) {
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1))) void first_conv_pool_kernel(
+    ConvArgs a, const float* __restrict__ wts, const float* __restrict__ bias, const float* __restrict__ den_map,
+    int cout_p, int total) {
   const int t = blockIdx.x * kThreads + threadIdx.x;
   if (t >= total) return;
   const int H = a.H, W = a.W, H2 = H >> 1, W2 = W >> 1, gq = W2 >> 2;
@@ -66,10 +55,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(DRSA_F
 
   const size_t plane2 = (size_t)H2 * W2;
   const size_t obase = ((size_t)b * a.cout) * plane2 + (size_t)qy * W2 + 4 * g4;
-  // den_ring_only (map den): the backward needs the per-sample copy only on the border ring of
-  // float4 groups (POST_DIV_RING; the map is one value per channel elsewhere), stored compactly:
+  // DEN 3 (den_ring_only; the host sends every such call here): the backward needs the per-sample
+  // copy only on the border ring of float4 groups (POST_DIV_RING; the map is one value per channel
+  // elsewhere), stored compactly:
   // per plane [row 0 | row H2-1 | rows 1..H2-2 x (first 4, last 4 columns)], coalesced float4s
-  const bool den_ring = (DEN == 1 && a.den_ring_only) || DEN == 3;
   const bool on_ring = qy == 0 || qy == H2 - 1 || g4 == 0 || 4 * g4 + 4 >= W2;
   const int ring_n = 2 * W2 + 8 * (H2 - 2);
   const int ring_i = qy == 0 ? 4 * g4 : qy == H2 - 1 ? W2 + 4 * g4 : 2 * W2 + (qy - 1) * 8 + (g4 == 0 ? 0 : 4);
@@ -78,7 +67,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(DRSA_F
   // blockIdx.y: channel slice (more waves in flight for the store stream)
   const int cper = (a.cout + gridDim.y - 1) / gridDim.y;
   const int c_lo = blockIdx.y * cper, c_hi = min(a.cout, c_lo + cper);
-#if DRSA_FIRST_FWD_PK
   // vertical pixel pairs of the patch: pr[ky][c] = (x[ky][c], x[ky + 1][c]), so one packed fma
   // (v_pk_fma_f32) advances the chains of the window's upper and lower pixel of one column
   fp2 pr[3][10];
@@ -86,12 +74,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(DRSA_F
   for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
     for (int c = 0; c < 10; ++c) pr[ky][c] = fp2{xin[ky][c], xin[ky + 1][c]};
-#endif
   // 32-bit offsets of the den map (C * H * W < 2^31, checked by the host)
   const int mrow = (2 * qy) * W + 8 * g4;
-#ifndef DRSA_FIRST_FWD_CUNROLL
-#define DRSA_FIRST_FWD_CUNROLL 4
-#endif
   // DEN 3: the channel loop keeps no map loads (none of its waits); each chunk of 32 channels
   // parks its argmax words in LDS (thread-private slots) and the ring lanes then gather the map
   // at their argmax pixels in a second, load-only pass
@@ -101,7 +85,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(DRSA_F
     const int ce = min(c_hi, cc + kChunk);
     // unrolled over channels: the next channels' weight / bias scalar loads issue ahead of this
     // channel's fma chains instead of one load latency per channel
-#pragma unroll DRSA_FIRST_FWD_CUNROLL
+#pragma unroll 4
     for (int co = cc; co < ce; ++co) {
       float w[NG][9];
 #pragma unroll
@@ -116,7 +100,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(DRSA_F
       for (int j = 0; j < 4; ++j) {
         // window pixels in torch's row-major order: s = 2 * py + px
         float yy[4];
-#if DRSA_FIRST_FWD_PK
         // the window's two columns as two interleaved chains (independent packed fmas back to back)
         fp2 acc[2] = {fp2{0.f, 0.f}, fp2{0.f, 0.f}};
 #pragma unroll
@@ -131,17 +114,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(DRSA_F
           yy[px] = z.x <= 0.f ? 0.f : z.x;
           yy[2 + px] = z.y <= 0.f ? 0.f : z.y;
         }
-#else
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int py = s >> 1, px = s & 1;
-          float acc = 0.f;
-#pragma unroll
-          for (int k = 0; k < 9; ++k) acc = __builtin_fmaf(xin[py + k / 3][2 * j + px + k % 3], w[0][k], acc);
-          const float z = acc + b0;
-          yy[s] = z <= 0.f ? 0.f : z;   // relu(NaN) = NaN
-        }
-#endif
         // torch max_pool2d: first maximum in window order; NaN wins (branch-free selects)
         int am = 0;
         float m = yy[0];
@@ -155,11 +127,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(DRSA_F
         ym[j] = m;
         amw |= (uint32_t)am << (8 * j);
         if constexpr (DEN == 1) {
-          // off the ring (den_ring) nothing is stored: those lanes read one address (an L1
-          // broadcast) instead of their scattered map pixel
           const int py = am >> 1, px = am & 1;
-          const int mi = co * H * W + mrow + py * W + 2 * j + px;
-          dn[j] = den_map[(den_ring && !on_ring) ? 0 : mi];
+          dn[j] = den_map[co * H * W + mrow + py * W + 2 * j + px];
         } else if constexpr (DEN == 2) {
           // the rule's denominator at the argmax pixel only (every chain is per pixel)
           float xs[9];
@@ -200,15 +169,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(DRSA_F
       if constexpr (DEN == 3) {
         am_sh[co - cc][threadIdx.x] = amw;
       } else if constexpr (DEN != 0) {
-        if (!den_ring)
-          *reinterpret_cast<float4*>(a.out_den + o) = make_float4(dn[0], dn[1], dn[2], dn[3]);
-        else if (on_ring)
-          *reinterpret_cast<float4*>(a.out_den + rbase + (size_t)co * ring_n) = make_float4(dn[0], dn[1], dn[2], dn[3]);
+        *reinterpret_cast<float4*>(a.out_den + o) = make_float4(dn[0], dn[1], dn[2], dn[3]);
       }
     }
     if constexpr (DEN == 3) {
       if (on_ring) {
-#pragma unroll DRSA_FIRST_FWD_RUNROLL
+        // 8 channels of gathers in flight (4: +3 %, 16: +1 %, micro-benchmark)
+#pragma unroll 8
         for (int co = cc; co < ce; ++co) {
           const uint32_t amw = am_sh[co - cc][threadIdx.x];
           float dn[4];
@@ -232,7 +199,7 @@ int launch_ng(const ConvArgs& a, int cout_p, int B, hipStream_t s) {
   const int cs = 1;
   const dim3 grid((total + kThreads - 1) / kThreads, cs);
   if (!a.out_den) hipLaunchKernelGGL((first_conv_pool_kernel<NG, 0>), grid, dim3(kThreads), 0, s, a, a.wts, a.bias, a.den_map, cout_p, total);
-  else if (a.den_map && a.den_ring_only && DRSA_FIRST_FWD_RING2)
+  else if (a.den_map && a.den_ring_only)
     hipLaunchKernelGGL((first_conv_pool_kernel<NG, 3>), grid, dim3(kThreads), 0, s, a, a.wts, a.bias, a.den_map, cout_p, total);
   else if (a.den_map) hipLaunchKernelGGL((first_conv_pool_kernel<NG, 1>), grid, dim3(kThreads), 0, s, a, a.wts, a.bias, a.den_map, cout_p, total);
   else hipLaunchKernelGGL((first_conv_pool_kernel<NG, 2>), grid, dim3(kThreads), 0, s, a, a.wts, a.bias, a.den_map, cout_p, total);

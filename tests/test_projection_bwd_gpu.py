@@ -1,8 +1,9 @@
 """drsa_amd_projection_bwd: the recompute path (h and a' rebuilt from a, the engine default) against
-the stored-buffer path, bitwise, over d (16 / 64 / 128: the register and the L1 a / den paths),
-K (d_k = 4, 8, 16, 32: the generic clone loop and its d_k = 16 form), fan-out modes, the pooled and
-the dense relevance input, and with and without the lower layer's denominator (den = NULL divides by
-nothing: x / 1 == x).  Reference: cxai/xai/explain/attribute.py:53-58 (SubspaceHook mask),
+the stored-buffer path, bitwise, over d (16 / 64 / 128: the register and the L1 a / den paths; 12 /
+24 / 100: the zero-padded embedding in the next wider kernel), K (d_k = 4, 8, 16, 25, 32: the generic
+clone loop and its d_k = 16 form), the tile shapes (8 x 8, 4 x 16, 2 x 32 pixels), fan-out modes, the
+pooled and the dense relevance input, and with and without the lower layer's denominator (den = NULL
+divides by nothing: x / 1 == x); and drsa_amd_projection_fwd without h against with h.  Reference: cxai/xai/explain/attribute.py:53-58 (SubspaceHook mask),
 cxai/model/modify_model.py:75-123 (ProjectionModel)."""
 import numpy as np
 import pytest
@@ -19,12 +20,8 @@ def _ortho(d, seed):
     return torch.from_numpy(q.astype(np.float32)).to(DEV)
 
 
-@pytest.mark.parametrize("D,K", [(16, 4), (64, 4), (64, 8), (64, 2), (128, 4)])
-@pytest.mark.parametrize("pool", [0, 1])
-@pytest.mark.parametrize("has_den", [True, False])
-@pytest.mark.parametrize("fanout", [0, 1, 2])
-def test_recompute_equals_stored(D, K, pool, has_den, fanout):
-    B, H, W = 3 if fanout == 0 else 2, 16, 16
+def _recompute_equals_stored(D, K, pool, has_den, fanout, H, W):
+    B = 3 if fanout == 0 else 2
     g = torch.Generator().manual_seed(D + 7 * K + 3 * pool + fanout)
     a = torch.randn(B, D, H, W, generator=g)
     # post-ReLU activations; the float64 check (fan-out 2) keeps a' away from 0, where fp32 and f64
@@ -82,3 +79,51 @@ def test_recompute_equals_stored(D, K, pool, has_den, fanout):
         got = outs[1].view(B, K, D, H, W)[:, q].double()
         scale = ref.abs().max().item() + 1e-30
         assert (got - ref).abs().max().item() / scale < 1e-4
+
+
+# d = DP (no padding code) and d < DP (12 -> 16, 24 -> 32, 100 -> 128: the VGGish width, d_k = 25)
+@pytest.mark.parametrize("D,K", [(16, 4), (64, 4), (64, 8), (64, 2), (128, 4), (12, 3), (24, 3), (100, 4)])
+@pytest.mark.parametrize("pool", [0, 1])
+@pytest.mark.parametrize("has_den", [True, False])
+@pytest.mark.parametrize("fanout", [0, 1, 2])
+def test_recompute_equals_stored(D, K, pool, has_den, fanout):
+    _recompute_equals_stored(D, K, pool, has_den, fanout, 16, 16)
+
+
+# the other tile shapes: W = 8 / 32 / 64 -> tiles of 8 x 8, 2 x 32, 2 x 32 pixels (RPT = 8, 2, 2)
+@pytest.mark.parametrize("D", [64, 100])
+@pytest.mark.parametrize("H,W", [(8, 8), (4, 32), (2, 64)])
+@pytest.mark.parametrize("pool", [0, 1])
+@pytest.mark.parametrize("fanout", [0, 1, 2])
+def test_recompute_equals_stored_tile_shapes(D, H, W, pool, fanout):
+    _recompute_equals_stored(D, 4, pool, True, fanout, H, W)
+
+
+@pytest.mark.parametrize("D", [16, 64, 128, 12, 24, 100])
+@pytest.mark.parametrize("pool", [0, 1])
+def test_forward_without_h_equals_with_h(D, pool):
+    """drsa_amd_projection_fwd with h = NULL (only the residual GEMM runs, U is not staged) writes the
+    same a', pooled a' and argmax, bit for bit, as the call that also stores h."""
+    B, H, W = 2, 16, 16
+    g = torch.Generator().manual_seed(100 + D + pool)
+    a = torch.randn(B, D, H, W, generator=g).clamp_min(0).to(DEV)
+    U = _ortho(D, D)
+    s = _capi.stream_ptr(DEV)
+    P = torch.empty_like(U)
+    _capi.call("drsa_amd_projection_residual", U.data_ptr(), D, P.data_ptr(), s)
+    outs = []
+    for with_h in (True, False):
+        h = torch.empty(B, D, H, W, device=DEV) if with_h else None
+        ap = torch.full((B, D, H, W), float("nan"), device=DEV)
+        pooled = torch.full((B, D, H // 2, W // 2), float("nan"), device=DEV) if pool else None
+        amax = torch.full((B, D, H // 2, W // 2), 255, dtype=torch.uint8, device=DEV) if pool else None
+        _capi.call("drsa_amd_projection_fwd", a.data_ptr(), U.data_ptr(), P.data_ptr(), _capi.ptr(h), ap.data_ptr(),
+                   _capi.ptr(pooled), _capi.ptr(amax), B, D, H, W, pool, s)
+        outs.append((ap, pooled, amax))
+    torch.cuda.synchronize()
+    assert not torch.isnan(outs[1][0]).any()
+    assert torch.equal(outs[0][0], outs[1][0])
+    if pool:
+        assert not torch.isnan(outs[1][1]).any() and (outs[1][2] < 4).all()
+        assert torch.equal(outs[0][1], outs[1][1])
+        assert torch.equal(outs[0][2], outs[1][2])
