@@ -67,6 +67,10 @@ SIGNATURES = {
     "drsa_amd_linear_fwd": (_i32, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _vp]),
     "drsa_amd_linear_bwd": (_i32, [_fp, _ip, _i32, _fp, _i32, _i32, _f32, _fp, _fp, _i32, _fp, _i32, _f32, _fp,
                                    _i32, _i32, _i32, _vp]),
+    "drsa_amd_linear_rule_fwd": (_i32, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32,
+                                        _vp]),
+    "drsa_amd_linear_rule_bwd": (_i32, [_fp, _ip, _i32, _fp, _i32, _fp, _fp, _i32, _i32, _f32, _fp, _fp, _fp, _i32,
+                                        _i32, _fp, _i32, _f32, _fp, _i32, _i32, _i32, _vp]),
     "drsa_amd_projection_residual": (_i32, [_fp, _i32, _fp, _vp]),
     "drsa_amd_projection_fwd": (_i32, [_fp, _fp, _fp, _fp, _fp, _fp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "drsa_amd_projection_bwd": (_i32, [_fp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32,

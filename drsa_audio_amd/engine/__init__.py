@@ -48,6 +48,44 @@ def _fingerprint(model):
             tuple((b.data_ptr(), b._version) for b in model.buffers()) + tuple(proj))
 
 
+def _rules_fingerprint(model, composite):
+    """The rule the composite gives every module, with its scalar parameters (gamma, stabilizer,
+    alpha, ...): the plan bakes them into prepared weight sets and constant denominators (conv and
+    dense alike), so two composites that differ only in one layer's rule or in its gamma have
+    different keys, and a rule edited in place on a cached composite recompiles."""
+    if composite is None:
+        return ()
+    out = []
+    for name, rule in sorted(composite.rules(model).items()):
+        fields = []
+        for k, v in sorted(getattr(rule, "__dict__", {}).items()):
+            v = _frozen(v)
+            if v is not _SKIP:
+                fields.append((k, v))
+        out.append((name, type(rule).__name__, tuple(fields)))
+    return tuple(out)
+
+
+_SKIP = object()
+
+
+def _frozen(v):
+    """A rule field as a hashable key part: scalars as they are, lists / tuples / sets (zero_params
+    may be given as any of them) as tuples, anything else (tensors, callables) left out."""
+    if v is None or isinstance(v, (bool, int, float, str)):
+        return v
+    if isinstance(v, (list, tuple, set, frozenset)):
+        items = sorted(v, key=repr) if isinstance(v, (set, frozenset)) else v
+        parts = tuple(_frozen(i) for i in items)
+        return _SKIP if any(p is _SKIP for p in parts) else parts
+    return _SKIP
+
+
+def cache_key(model, composite):
+    """What a cached plan is valid for: the model's tensors, the composite's rules, the engine options."""
+    return (_fingerprint(model), _rules_fingerprint(model, composite), bf16_backward_default())
+
+
 def _ref(obj):
     if obj is None:
         return lambda: None
@@ -65,7 +103,7 @@ def _evict(key) -> None:
 def get_engine(model, composite) -> LRPEngine:
     """Compiled plan for (model, composite), cached while the model's parameters are unchanged."""
     key = (id(model), id(composite))
-    fp = (_fingerprint(model), bf16_backward_default())   # the option selects different kernels
+    fp = cache_key(model, composite)   # the bf16_backward option selects different kernels
     e = _CACHE.get(key)
     if e is not None:
         if e.model_ref() is model and e.comp_ref() is composite and e.fp == fp:

@@ -15,7 +15,11 @@ Backward: one ``drsa_amd_conv_bwd`` per conv stage, the max-pool/ReLU backward f
 into its input, the next lower layer's division folded into its output.  The subspace
 path fans one forward out into K+1 relevance clones at the projection
 (``drsa_amd_projection_bwd``), instead of replicating the batch K+1 times
-(explainer.py:92).
+(explainer.py:92).  A dense stage under Epsilon (or no rule) is one ``drsa_amd_linear_fwd`` and one
+``drsa_amd_linear_bwd``; under Gamma / ZPlus its forward also writes the rule's denominators
+(``drsa_amd_linear_rule_fwd``) and under Gamma / ZPlus / WSquare / Flat its backward is one
+``drsa_amd_linear_rule_bwd`` with a chain per term of R_in (pf.py:18-27, 257-292: the dense rule
+comes from the same rule_mapper as the conv rule).
 
 Weights are prepared on the device once per plan (rule-modified, flipped/transposed for
 the backward, padded to the kernels' channel tiles).  Activation buffers are cached per
@@ -65,6 +69,14 @@ def _pad32(c: int) -> int:
 
 def _cin_pad(c: int) -> int:
     return 1 if c == 1 else _pad32(c)
+
+
+def _proj_hw(h: int, w: int) -> Tuple[int, int]:
+    """The map size the projection kernels tile for an h x w map (W 8, 16 or a multiple of 32, H a
+    multiple of 64 / min(W, 32) rows): (h, w) itself wherever they take it as it is."""
+    wk = 8 if w <= 8 else 16 if w <= 16 else _pad32(w)
+    rows = 64 // min(wk, 32)
+    return (h + rows - 1) // rows * rows, wk
 
 
 def _kind(rule) -> Optional[str]:
@@ -136,10 +148,64 @@ class DenseStage:
     rule_kind: Optional[str]
     eps: float
     relu_after: bool
+    input_nonneg: bool = False           # the layer's input is known >= 0: the rule's x- terms are dropped
+    # Gamma / ZPlus / WSquare / Flat: dense_rule_params(W, b, rule) on the device (None: Epsilon / no rule)
+    rp: Optional[dict] = None
+    # relevance arriving through the ReLU after the layer is masked by [z > 0].  Not so when that ReLU
+    # carries Pass (the gradient passes unchanged) and the next dense layer is WSquare / Flat, whose
+    # R_in is not multiplied by its input and so is not already zero where z <= 0
+    mask: bool = False
+    relu_pass: bool = False              # the ReLU after the layer carries Pass
+
+    @property
+    def split(self) -> bool:             # Gamma / ZPlus: modified weight sets and per-sample denominators
+        return self.rule_kind in ("gamma", "zplus")
+
+    @property
+    def negden(self) -> bool:            # Gamma with unmasked relevance: [z < 0] can hold, den_n is needed
+        return self.rule_kind == "gamma" and not self.mask
 
 
 class EngineError(NotImplementedError):
     pass
+
+
+DENSE_RULES = (None, "epsilon", "gamma", "zplus", "wsquare", "flat")
+
+
+@torch.no_grad()
+def dense_rule_params(W: torch.Tensor, b: Optional[torch.Tensor], rule) -> dict:
+    """The parameter sets of a rule on a dense layer (weight ``W [N][K]``, bias ``b`` or None), as
+    plan constants: the oracle's own expressions (oracle/lrp_ref.py rule_backward_analytic), two
+    roundings each, evaluated once in fp32 where ``W`` lives (the plan calls it on the host).
+
+      gamma    Wp, Wn = W + g W.clamp(min=0), W + g W.clamp(max=0);  bp, bn likewise
+      zplus    Wp, Wn = W.clamp(min=0), W.clamp(max=0);  bp = b.clamp(min=0), bn = None
+      wsquare  W2, b2 = W W, b b;  den [N] = f(1; W2, b2): one k-ascending fp32 chain per output
+               neuron, the bias added last -- it does not depend on the input
+      flat     W2, b2 = 1, 0;  den likewise
+    ``kind`` and ``eps`` are always present; Epsilon / Norm / no rule need nothing else."""
+    kind = _kind(rule)
+    if kind not in DENSE_RULES:
+        raise EngineError(f"engine: rule {type(rule).__name__} on a dense layer is not supported")
+    out = {"kind": kind, "eps": 0.0 if kind is None else float(_eps_of(rule))}
+    mod = lambda fn: None if b is None else fn(b)       # noqa: E731
+    if kind == "gamma":
+        g = rule.gamma
+        out.update(Wp=W + g * W.clamp(min=0), Wn=W + g * W.clamp(max=0),
+                   bp=mod(lambda t: t + g * t.clamp(min=0)), bn=mod(lambda t: t + g * t.clamp(max=0)))
+    elif kind == "zplus":
+        out.update(Wp=W.clamp(min=0), Wn=W.clamp(max=0), bp=mod(lambda t: t.clamp(min=0)), bn=None)
+    elif kind in ("wsquare", "flat"):
+        if kind == "wsquare":
+            W2, b2 = W * W, mod(lambda t: t * t)
+        else:
+            W2, b2 = torch.ones_like(W), mod(torch.zeros_like)
+        acc = torch.zeros(W.size(0), dtype=W.dtype, device=W.device)
+        for col in W2.t().contiguous():          # fmaf(1, w2, acc) = fl(acc + w2), k ascending
+            acc = acc + col
+        out.update(W2=W2, b2=b2, den=acc if b2 is None else acc + b2)
+    return out
 
 
 class LRPEngine:
@@ -176,6 +242,17 @@ class LRPEngine:
         self._buffers: Dict[tuple, dict] = {}
         self.last: Optional[dict] = None
         self.trace: Optional[list] = None      # set to [] to record (tag, start_event, end_event)
+
+    @classmethod
+    def check(cls, model: nn.Module, composite) -> None:
+        """The parse step of a plan alone, on the host: raises the EngineError that compiling the
+        plan for ``model`` under ``composite`` would raise, and prepares nothing.  Needs no GPU for a
+        model without ProjectionModel layers."""
+        eng = cls.__new__(cls)
+        eng.device, eng.bf16, eng.stages, eng.dense = torch.device("cpu"), False, [], []
+        rules = composite.rules(model) if composite is not None else {}
+        merge_bn = any(isinstance(c, SequentialMergeBatchNorm) for c in getattr(composite, "canonizers", []))
+        eng._parse(model, rules, merge_bn)
 
     @property
     def model(self):
@@ -304,23 +381,43 @@ class LRPEngine:
                     raise EngineError("BatchNorm1d in the head needs the SequentialMergeBatchNorm canonizer")
                 W, b = SequentialMergeBatchNorm.fold(W, b, _bn_to(cl[j][1], torch.device("cpu")))
                 j += 1
-            W = W.to(self.device)
-            b = None if b is None else b.to(self.device)
-            relu = False
+            relu = relu_pass = False
             while j < n and isinstance(cl[j][1], (nn.ReLU, nn.Dropout)):
                 if isinstance(cl[j][1], nn.ReLU):
                     relu = True
                     self._rule_ok_on_activation(rules.get(f"classifier.{cl[j][0]}"))
+                    relu_pass = rules.get(f"classifier.{cl[j][0]}") is not None
                 j += 1
             rule = rules.get(f"classifier.{name}")
             kind = _kind(rule)
-            if kind not in (None, "epsilon"):
+            if self.dense and self.dense[-1].relu_pass and kind in ("wsquare", "flat"):
+                self.dense[-1].mask = False      # see DenseStage.mask
+            if not self.dense and kind in ("wsquare", "flat"):
+                # towards the trunk there is no such unmasked path: the hand-off to the last conv stage
+                # masks by [a > 0] and the conv rules form no [z < 0] branch (Gamma: no den_n), while a
+                # Pass on that stage's ReLU lets WSquare / Flat relevance through where a = 0.  Refused
+                # whatever the conv's rule; with the ReLU unmapped autograd's own mask is the hand-off's
+                lst = self.stages[-1]
+                if lst.proj is None and rules.get(lst.relu_name) is not None:
+                    raise EngineError(f"engine: {type(rule).__name__} on classifier.{name} above a Pass on the last "
+                                      f"conv block's activation ({lst.relu_name}) is not supported: leave that "
+                                      "activation unmapped")
+            if kind not in DENSE_RULES:
                 raise EngineError(f"engine: rule {type(rule).__name__} on classifier.{name} is not supported yet")
             if rule is not None and "bias" in getattr(rule, "zero_params", ()):
                 raise EngineError("engine: zero_params on dense layers is not supported yet")
+            # the rule's weight sets / constant denominator are prepared on the host, as the conv
+            # sets are prepared once per plan, and moved to the device with W
+            rp = dense_rule_params(W, b, rule) if kind in ("gamma", "zplus", "wsquare", "flat") else None
+            if rp is not None:
+                rp = {k: v.to(self.device).contiguous() if isinstance(v, torch.Tensor) else v for k, v in rp.items()}
+            W = W.to(self.device)
+            b = None if b is None else b.to(self.device)
             self.dense.append(DenseStage(name=f"classifier.{name}", W=W.contiguous(),
                                          b=None if b is None else b.contiguous(), rule_kind=kind,
-                                         eps=_eps_of(rule) if kind else 0.0, relu_after=relu))
+                                         eps=_eps_of(rule) if kind else 0.0, relu_after=relu,
+                                         input_nonneg=prev_nonneg, rp=rp, mask=relu, relu_pass=relu_pass))
+            prev_nonneg = relu
             i = j
         if not self.stages or not self.dense:
             raise EngineError("engine: model must have a conv trunk and a dense head")
@@ -519,6 +616,17 @@ class LRPEngine:
             self._cur_bufs[key] = t
         return t
 
+    def _pad_map(self, key, t: torch.Tensor, hk: int, wk: int) -> torch.Tensor:
+        """``t [n][c][h][w]`` copied into the top-left corner of a cached ``[n][c][hk][wk]`` buffer whose
+        remainder is zero (zeroed when the buffer is made; only the corner is ever written)."""
+        shape = (t.size(0), t.size(1), hk, wk)
+        p = self._cur_bufs.get(key)
+        if p is None or tuple(p.shape) != shape:
+            p = torch.zeros(shape, dtype=t.dtype, device=self.device)
+            self._cur_bufs[key] = p
+        p[:, :, :t.size(2), :t.size(3)].copy_(t)
+        return p
+
     # ---------------------------------------------------------------- forward
     @torch.no_grad()
     def forward(self, x: torch.Tensor, capture: Optional[int] = None) -> torch.Tensor:
@@ -608,23 +716,31 @@ class LRPEngine:
                     P = st.proj
                     # h and a' are recomputed by projection_bwd from a (no HBM round trip); a' is
                     # stored only when it is the stage output (no pool after the projection)
-                    hb = self._buf((li, "h"), (B, st.cout, h * w)) if _PROJ_STORE else None
-                    ap = self._buf((li, "ap"), (B, st.cout, h, w)) if (_PROJ_STORE or not P.pool_after) else None
+                    # a map smaller than the projection kernels tile (the toy net's last block: 4 x 4) runs
+                    # zero-padded at its right and bottom: every pixel and every 2 x 2 window is on its
+                    # own there, and the kernel-side buffers (a, h, a', pooled, argmax) keep that size
+                    hk, wk = _proj_hw(h, w)
+                    padded = (hk, wk) != (h, w)
+                    ak = self._pad_map((li, "a_pad"), a, hk, wk) if padded else a
+                    hb = self._buf((li, "h"), (B, st.cout, hk * wk)) if _PROJ_STORE else None
+                    ap = self._buf((li, "ap"), (B, st.cout, hk, wk)) if (_PROJ_STORE or not P.pool_after) else None
                     if P.pool_after:
-                        pooled = self._buf((li, "y"), (B, st.cout, h // 2, w // 2))
-                        amax = self._buf((li, "amax"), (B, st.cout, h // 2, w // 2), torch.uint8)
+                        pooled = self._buf((li, "y_pad" if padded else "y"), (B, st.cout, hk // 2, wk // 2))
+                        amax = self._buf((li, "amax"), (B, st.cout, hk // 2, wk // 2), torch.uint8)
                     else:
                         pooled = amax = None
-                    self._call("projection_fwd", "drsa_amd_projection_fwd", a.data_ptr(), P.U.data_ptr(), P.P.data_ptr(),
+                    self._call("projection_fwd", "drsa_amd_projection_fwd", ak.data_ptr(), P.U.data_ptr(), P.P.data_ptr(),
                                _capi.ptr(hb), _capi.ptr(ap),
-                               _capi.ptr(pooled), _capi.ptr(amax), B, st.cout, h, w, 1 if P.pool_after else 0, s)
-                    rec.update(h=hb, ap=ap, amax=amax)
+                               _capi.ptr(pooled), _capi.ptr(amax), B, st.cout, hk, wk, 1 if P.pool_after else 0, s)
+                    rec.update(h=hb, ap=ap, amax=amax, a_k=ak, pad=(hk, wk) if padded else None)
+                    y = pooled if P.pool_after else ap
                     if P.pool_after:
-                        rec.update(y=pooled, Hout=h // 2, Wout=w // 2)
-                        cur, h, w = pooled, h // 2, w // 2
-                    else:
-                        rec.update(y=ap, Hout=h, Wout=w)
-                        cur = ap
+                        h, w = h // 2, w // 2
+                    if padded:
+                        y = self._buf((li, "y" if P.pool_after else "ap_crop"), (B, st.cout, h, w))
+                        y.copy_((pooled if P.pool_after else ap)[:, :, :h, :w])
+                    rec.update(y=y, Hout=h, Wout=w)
+                    cur = y
                 else:
                     rec.update(y=a, Hout=h, Wout=w)
                     cur = a
@@ -639,9 +755,20 @@ class LRPEngine:
             N, Kd = ds.W.shape
             z = self._buf(("d", di, "z"), (B, N))
             act = self._buf(("d", di, "a"), (B, N)) if ds.relu_after else None
-            self._call(f"linear_fwd:{ds.name}", "drsa_amd_linear_fwd", inp.data_ptr(), ds.W.data_ptr(), _capi.ptr(ds.b), z.data_ptr(),
-                       _capi.ptr(act), B, N, Kd, s)
-            dense_recs.append({"x": inp, "z": z, "a": act})
+            den_p = den_n = None
+            if ds.split:
+                # Gamma / ZPlus: z and the rule's denominators in one launch over one staged x
+                rp, signed = ds.rp, not ds.input_nonneg
+                den_p = self._buf(("d", di, "den_p"), (B, N))
+                den_n = self._buf(("d", di, "den_n"), (B, N)) if ds.negden else None
+                self._call(f"linear_rule_fwd:{ds.name}", "drsa_amd_linear_rule_fwd", inp.data_ptr(), ds.W.data_ptr(),
+                           rp["Wp"].data_ptr(), rp["Wn"].data_ptr() if (signed or ds.negden) else None, _capi.ptr(ds.b),
+                           _capi.ptr(rp["bp"]), _capi.ptr(rp["bn"]) if ds.negden else None, z.data_ptr(),
+                           _capi.ptr(act), den_p.data_ptr(), _capi.ptr(den_n), 1 if signed else 0, B, N, Kd, s)
+            else:
+                self._call(f"linear_fwd:{ds.name}", "drsa_amd_linear_fwd", inp.data_ptr(), ds.W.data_ptr(), _capi.ptr(ds.b), z.data_ptr(),
+                           _capi.ptr(act), B, N, Kd, s)
+            dense_recs.append({"x": inp, "z": z, "a": act, "den_p": den_p, "den_n": den_n})
             inp = act if act is not None else z
         state["dense"] = dense_recs
         self.last = state
@@ -691,10 +818,28 @@ class LRPEngine:
                 x_mask = rec["x"]
             else:
                 x_mask = rec["x"]
-            relu_mask = 1 if ds.relu_after else 0
+            relu_mask = 1 if ds.mask else 0
             xmode = XM_MUL if ds.rule_kind == "epsilon" else XM_NONE
             den_flat = None if den is None else den.reshape(B, -1)
-            if di == len(self.dense) - 1 and cls is not None:
+            seeded = di == len(self.dense) - 1 and cls is not None
+            if ds.rp is not None:
+                # Gamma / ZPlus / WSquare / Flat: one launch, every term of R_in its own chain over one staged g
+                if not seeded:
+                    if R is None:
+                        raise ValueError("backward needs a seed or class indices")
+                    R = R.to(self.device, torch.float32).contiguous()
+                rp, signed = ds.rp, ds.split and not ds.input_nonneg
+                if ds.split:
+                    dp, dn, bcast, xmul = rec["den_p"], rec["den_n"], 0, 1
+                    Wp, Wn = rp["Wp"], rp["Wn"] if (signed or ds.negden) else None
+                else:
+                    dp, dn, bcast, xmul, Wp, Wn = rp["den"], None, 1, 0, rp["W2"], None
+                self._call(f"linear_rule_bwd:{ds.name}", "drsa_amd_linear_rule_bwd", None if seeded else R.data_ptr(),
+                           cls.data_ptr() if seeded else None, 1 if (seeded and one_hot) else 0, rec["z"].data_ptr(),
+                           relu_mask, dp.data_ptr(), _capi.ptr(dn), bcast, 1 if ds.rule_kind == "gamma" else 0, ds.eps,
+                           Wp.data_ptr(), _capi.ptr(Wn), x_mask.data_ptr(), xmul, 1 if signed else 0,
+                           _capi.ptr(den_flat), post, eps_post, out.data_ptr(), B, N, Kd, s)
+            elif seeded:
                 self._call(f"linear_bwd:{ds.name}", "drsa_amd_linear_bwd", None, cls.data_ptr(), 1 if one_hot else 0, rec["z"].data_ptr(),
                            relu_mask, 1 if ds.rule_kind == "epsilon" else 0, ds.eps, ds.W.data_ptr(),
                            x_mask.data_ptr(), xmode, _capi.ptr(den_flat), post, eps_post, out.data_ptr(), B, N, Kd, s)
@@ -726,11 +871,19 @@ class LRPEngine:
                                   else (POST_MASK, None, 0.0))
                 if not P.mask:
                     raise EngineError("engine: projection without SubspaceHook is not supported yet")
-                self._call("projection_bwd", "drsa_amd_projection_bwd", g.data_ptr(), _capi.ptr(rec["amax"] if P.pool_after else None),
-                           _capi.ptr(rec["ap"] if _PROJ_STORE else None), _capi.ptr(rec["h"]), rec["a"].data_ptr(),
-                           _capi.ptr(den if post == POST_DIV else None), P.U.data_ptr(), P.P.data_ptr(), G.data_ptr(),
+                hk, wk = rec["pad"] or (h, w)
+                gk, Gk, denk = g, G, den if post == POST_DIV else None
+                if rec["pad"]:      # the forward's zero-padded map: g and den padded alike, G cropped
+                    gk = self._pad_map((li, "g_pad"), g, *((hk // 2, wk // 2) if P.pool_after else (hk, wk)))
+                    denk = None if denk is None else self._pad_map((li, "den_pad"), denk, hk, wk)
+                    Gk = self._buf((li, "G_pad"), (B * nq, st.cout, hk, wk))
+                self._call("projection_bwd", "drsa_amd_projection_bwd", gk.data_ptr(), _capi.ptr(rec["amax"] if P.pool_after else None),
+                           _capi.ptr(rec["ap"] if _PROJ_STORE else None), _capi.ptr(rec["h"]), rec["a_k"].data_ptr(),
+                           _capi.ptr(denk), P.U.data_ptr(), P.P.data_ptr(), Gk.data_ptr(),
                            B, st.cout,
-                           h, w, K, P.eps_inv, eps, fan, s)
+                           hk, wk, K, P.eps_inv, eps, fan, s)
+                if rec["pad"]:
+                    G.copy_(Gk[:, :, :h, :w])
                 g, clones, Bq = G, nq, B * nq
             elif st.pool and st.pool_k == (2, 2):
                 amax_in = rec["amax"]

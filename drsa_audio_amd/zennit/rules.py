@@ -13,6 +13,25 @@ Semantics (reference name maps ``constants.py:27-51``):
                one denominator per set; R_in = α·pos − β·neg (HIP engine: convs with a non-negative
                input; elsewhere compiling the composite raises ``EngineError``)
   Norm(ε)      ≡ Epsilon(ε) on conv/dense layers
+Every rule but AlphaBeta and Pass also compiles on the dense head (``classifier.*``), with the same
+semantics on ``f = Linear`` and a signed or non-negative input:
+
+  rule      conv trunk                      dense head
+  Epsilon   yes                             yes
+  Norm      yes (≡ Epsilon)                 yes (≡ Epsilon)
+  Gamma     yes                             yes (den- too where no ReLU follows the layer)
+  ZPlus     yes                             yes
+  WSquare   yes                             yes (den = f(1; W², b²), one constant per output neuron);
+                                            on ``classifier.0`` only with the last conv's ReLU unmapped
+  Flat      yes                             as WSquare
+  AlphaBeta non-negative input only         ``EngineError``
+  Pass      activations only                activations only
+``zero_params`` on a dense layer raises ``EngineError``.
+WSquare / Flat do not multiply by the layer's input, so under a Pass on the ReLU below them relevance
+reaches units with z <= 0.  Inside the head the plan runs that case (the layer below takes unmasked
+relevance).  On ``classifier.0`` above a Pass on the last conv block's ReLU it raises ``EngineError``:
+the conv kernels have no [z < 0] branch.  ``PixelFlipping`` maps Pass to every activation, so its
+``'dense'`` key cannot name ``wsquare`` or ``flat``.
 A ``Hook`` subclass with its own ``backward`` (not a descriptor) runs on the autograd slow path
 (``engine/hooks.py``).
 """

@@ -265,6 +265,32 @@ int drsa_amd_linear_bwd(const float* R, const int* seed_cls, int one_hot, const 
                         float eps, const float* W, const float* x, int xmode, const float* den, int post,
                         float eps_post, float* out, int M, int Nout, int Kin, void* stream);
 
+/* Dense layer under Gamma / ZPlus / WSquare / Flat (reference pf.py:18-27, 257-292: the dense rule
+ * comes from the same rule_mapper as the conv rule; zennit rule semantics per SURVEY Appendix A).
+ * Wp / Wn and bias_p / bias_n are the rule's modified parameter sets, prepared once by the plan
+ * (Gamma: W + gamma W+-; ZPlus: W+-, b+).
+ *
+ * Forward, one launch: z = x W^T + b (bit-identical to drsa_amd_linear_fwd) [, relu(z)] and
+ *   den_p = f(x+; Wp, bias_p) + f(x-; Wn, 0)
+ *   den_n = f(x+; Wn, bias_n) + f(x-; Wp, 0)      (only when den_n is given: Gamma without a ReLU after)
+ * every term its own k-ordered chain with its bias added last.  x_signed = 0 declares x >= 0: the x-
+ * terms are dropped (exactly zero) and x+ = x.  Wn is required when x_signed or den_n.
+ *
+ * Backward, one launch: with R = seed | incoming relevance (through the ReLU mask),
+ *   g_p = R [z > 0 when zsign] / stab(den_p, eps),  g_n = R [z < 0] / stab(den_n, eps)  (den_n given)
+ *   out = epi( x+ (g_p Wp) + x- (g_p Wn) + x+ (g_n Wn) + x- (g_n Wp) )   summed left to right,
+ * the x- terms only when x_signed, the g_n terms only when den_n is given.  xmul = 0 (WSquare / Flat,
+ * Wp = W2): out = epi(g_p Wp) with den_p the plan's constant [Nout] (den_bcast = 1).  seed_cls and
+ * den / post / eps_post as for drsa_amd_linear_bwd (POST_NONE, POST_DIV or POST_MASK). */
+int drsa_amd_linear_rule_fwd(const float* x, const float* W, const float* Wp, const float* Wn, const float* bias,
+                             const float* bias_p, const float* bias_n, float* z_out, float* relu_out, float* den_p,
+                             float* den_n, int x_signed, int M, int N, int K, void* stream);
+int drsa_amd_linear_rule_bwd(const float* R, const int* seed_cls, int one_hot, const float* z, int relu_mask,
+                             const float* den_p, const float* den_n, int den_bcast, int zsign, float eps,
+                             const float* Wp, const float* Wn, const float* x, int xmul, int x_signed,
+                             const float* den, int post, float eps_post, float* out, int M, int Nout, int Kin,
+                             void* stream);
+
 /* Projection residual P = U U^T - I (d x d, d <= 128): each entry a float64 fma chain over k
  * ascending minus the identity, rounded once to fp32 (symmetric bit for bit).  Computed once per
  * U (plan preparation); the projection calls below evaluate a' = h U^T as a + a P, so that a' at
