@@ -647,8 +647,11 @@ class LRPEngine:
         cur, h, w = x, H, W
         for li, st in enumerate(self.stages):
             ph, pw = st.pool_k if st.pool else (1, 1)
-            if h % 2 or w % 2 or h % ph or w % pw:
-                raise ValueError(f"{st.name}: feature map {h}x{w} must have even sides divisible by the pool")
+            # w % 4: the conv's rule backward and its unpooled forward move float4 rows (the C entry
+            # points refuse other widths), so a map the backward could not cross is refused here
+            if h % 2 or w % 4 or h % ph or w % pw:
+                raise ValueError(f"{st.name}: feature map {h}x{w} must have an even height, a width divisible by 4 "
+                                 f"and sides divisible by the pool")
             rec = {"in": cur, "H": h, "W": w}
             den_map = self._den_map(st, h, w) if st.den_kind == "map" else None
             need_den = st.den_kind is not None
