@@ -1,4 +1,4 @@
-"""HIP LRP engine: plan compilation + execution (see ``plan.py``).
+"""HIP LRP engine: plan compilation (``parse.py``, ``plan.py``, ``schedule.py``) + execution (``plan.py``).
 
 ``get_engine`` caches compiled plans per (model, composite) while the model's parameters are
 unchanged.  The cache holds the model and the composite only through weak references (the

@@ -7,7 +7,7 @@ the tests built on it compare with torch.equal.
 
 Weights are given as forward-shaped sets [cout][cin][3][3] (the conv that maps cin -> cout
 channels); ``pack_fwd`` / ``pack_bwd`` / ``pack_bf16`` lay them out for the device as
-engine/plan.py's _prepare_conv does.  A backward call of the ABI names its channels the other way
+engine/plan.py's prepare step (_prepare_conv) does.  A backward call of the ABI names its channels the other way
 round: its ``cin`` is the forward cout (the channels of g), its ``cout`` the forward cin.
 
 The keyword arguments ``pad``, ``tie``, ``mask_ge`` and ``stab_plus`` select deliberately WRONG

@@ -37,7 +37,7 @@ def spec(name_map):
         elif k in ("wsquare", "flat", "zplus"):
             t = (k, r.stabilizer)
         elif k == "norm":
-            # zennit Norm(stabilizer) on conv/dense = Epsilon(stabilizer) (see engine/plan.py _kind)
+            # zennit Norm(stabilizer) on conv/dense = Epsilon(stabilizer) (see engine/parse.py _kind)
             t = ("epsilon", r.stabilizer)
         elif k == "alphabeta":
             t = ("alphabeta", r.alpha, r.beta, r.stabilizer)

@@ -1,6 +1,6 @@
 """Truth table of the four conv ``*_has_kernel*`` queries (csrc/lrp_conv.hip), pinned.
 
-The engine picks its entry points by these answers (engine/plan.py), so a changed answer changes
+The engine picks its entry points by these answers (engine/schedule.py), so a changed answer changes
 which kernels a model runs.  The queries do no device work: this runs without a GPU.
 
 ``tests/golden/conv_has_kernel.json`` holds, per query, the axes swept and the answers as one string
