@@ -44,6 +44,11 @@ SIGNATURES = {
     "drsa_amd_polar": (_i32, [_fp, _i32, _fp, _ip, _vp]),
     "drsa_amd_subspace_relevances_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "drsa_amd_subspace_relevances": (_i32, [_fp, _fp, _i64, _i64, _i32, _i32, _fp, _fp, _vp, _sz, _vp]),
+    "drsa_amd_prca_workspace_bytes": (_sz, [_i64, _i32]),
+    "drsa_amd_prca_partial": (_i32, [_fp, _fp, _i64, _i32, _fp, _vp, _sz, _vp]),
+    "drsa_amd_prca_finish": (_i32, [_fp, _i64, _i32, _fp, _vp]),
+    "drsa_amd_syevj_workspace_bytes": (_sz, [_i32]),
+    "drsa_amd_syevj": (_i32, [_fp, _i32, _fp, _fp, _ip, _vp, _sz, _vp]),
     "drsa_amd_conv_weight_floats": (_sz, [_i32, _i32, _i32]),
     "drsa_amd_conv_fwd": (_i32, [_fp, _fp, _fp, _fp, _fp, _vp, _fp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "drsa_amd_conv_weight_bf16_elems": (_sz, [_i32, _i32, _i32]),

@@ -9,6 +9,7 @@
 //   drsa_step / drsa_objective / drsa_run   cxai/xai/drsa/drsa.py:84-106, 122-155, 76-120
 //   polar                                   drsa.py:201-221 (orthogonalize)
 //   subspace_relevances                     cxai/xai/explain/explainer.py:206-242
+//   prca_covariance / syevj                 PRCA (no reference counterpart; csrc/prca.hip)
 //   lrp_conv_fwd / lrp_conv_bwd / lrp_linear_fwd / lrp_linear_bwd / projection_fwd / projection_bwd
 //                                           the zennit rule passes attribute.py:98-107 drives
 //   heatmap_sort                            explainer.py:99-123, 151-176
@@ -183,6 +184,40 @@ Tensor subspace_relevances(const Tensor& act, const Tensor& ctx, const Tensor& U
   return out;
 }
 
+Tensor prca_covariance(const Tensor& A, const Tensor& C) {
+  DRSA_GUARD(A);
+  need(A, "activation_vecs"), need(C, "context_vecs");
+  same_device(A, {&C});
+  TORCH_CHECK(A.dim() == 2 && A.sizes() == C.sizes(), "drsa_amd: activation and context vectors must be [N, d]");
+  const int64_t N = A.size(0), d = A.size(1);
+  const size_t nb = drsa_amd_prca_workspace_bytes(N, (int)d);
+  TORCH_CHECK(nb > 0, "drsa_amd: unsupported PRCA problem N=", N, " d=", d, " (N >= 1, 1 <= d <= 128)");
+  Tensor ws = at::empty({(int64_t)nb}, A.options().dtype(at::kByte));
+  Tensor slab = at::empty({d, d}, A.options());
+  Tensor M = at::empty({d, d}, A.options());
+  check(drsa_amd_prca_partial(A.data_ptr<float>(), C.data_ptr<float>(), N, (int)d, slab.data_ptr<float>(),
+                              ws.data_ptr(), nb, cur_stream()),
+        "prca_covariance");
+  check(drsa_amd_prca_finish(slab.data_ptr<float>(), N, (int)d, M.data_ptr<float>(), cur_stream()), "prca_covariance");
+  return M;
+}
+
+std::tuple<Tensor, Tensor> syevj(const Tensor& M) {
+  DRSA_GUARD(M);
+  need(M, "M");
+  TORCH_CHECK(M.dim() == 2 && M.size(0) == M.size(1), "drsa_amd: syevj needs a square matrix");
+  const int64_t d = M.size(0);
+  const size_t nb = drsa_amd_syevj_workspace_bytes((int)d);
+  TORCH_CHECK(nb > 0, "drsa_amd: unsupported syevj size d=", d, " (1..128)");
+  Tensor ws = at::empty({(int64_t)nb}, M.options().dtype(at::kByte));
+  Tensor w = at::empty({d}, M.options());
+  Tensor V = at::empty({d, d}, M.options());
+  check(drsa_amd_syevj(M.data_ptr<float>(), (int)d, w.data_ptr<float>(), V.data_ptr<float>(), nullptr, ws.data_ptr(),
+                       nb, cur_stream()),
+        "syevj");
+  return {w, V};
+}
+
 std::tuple<Tensor, Tensor, Tensor> lrp_conv_fwd(const Tensor& x, const Tensor& wts, const Tensor& bias3,
                                                 const c10::optional<Tensor>& den_map, int64_t cout, int64_t ng,
                                                 bool pool) {
@@ -318,6 +353,8 @@ TORCH_LIBRARY(drsa_amd, m) {
   m.def("drsa_run(Tensor A, Tensor C, Tensor U0, int K, int steps) -> (Tensor, Tensor)");
   m.def("polar(Tensor V) -> Tensor");
   m.def("subspace_relevances(Tensor act, Tensor ctx, Tensor U, int K) -> Tensor");
+  m.def("prca_covariance(Tensor A, Tensor C) -> Tensor");
+  m.def("syevj(Tensor M) -> (Tensor, Tensor)");
   m.def("lrp_conv_fwd(Tensor x, Tensor wts, Tensor bias3, Tensor? den_map, int cout, int ng, bool pool) "
         "-> (Tensor, Tensor, Tensor)");
   m.def("lrp_conv_bwd(Tensor g, Tensor? amax, Tensor wts, Tensor? x, Tensor? den, int cin, int H, int W, "
@@ -337,6 +374,8 @@ TORCH_LIBRARY_IMPL(drsa_amd, CUDA, m) {
   m.impl("drsa_run", &drsa_run);
   m.impl("polar", &polar);
   m.impl("subspace_relevances", &subspace_relevances);
+  m.impl("prca_covariance", &prca_covariance);
+  m.impl("syevj", &syevj);
   m.impl("lrp_conv_fwd", &lrp_conv_fwd);
   m.impl("lrp_conv_bwd", &lrp_conv_bwd);
   m.impl("lrp_linear_fwd", &lrp_linear_fwd);

@@ -16,6 +16,8 @@ message; there is no CPU kernel (a CPU tensor raises); a missing ``libdrsa_amd_t
   drsa_amd::drsa_run(A, C, U0, K, steps) -> (U, traj)        drsa.py:76-120 (traj: steps+1)
   drsa_amd::polar(V) -> U                                    drsa.py:201-221 (orthogonalize)
   drsa_amd::subspace_relevances(act, ctx, U, K) -> r         explainer.py:206-242
+  drsa_amd::prca_covariance(A, C) -> M                       PRCA: (A^T C + C^T A) / (2N)
+  drsa_amd::syevj(M) -> (w, V)                               symmetric eigh, descending (csrc/prca.hip)
   drsa_amd::lrp_conv_fwd(x, wts, bias3, den_map?, cout, ng, pool) -> (y, amax, den)
   drsa_amd::lrp_conv_bwd(g, amax?, wts, x?, den?, cin, H, W, clones, ng, xmode, post, eps) -> R
   drsa_amd::lrp_linear_fwd(x, W, b?, relu) -> (z, a)
@@ -93,6 +95,16 @@ def _(act, ctx, U, K):
     return act.new_empty(b, K, dtype=torch.float32)
 
 
+@_fake("prca_covariance")
+def _(A, C):
+    return A.new_empty(A.shape[1], A.shape[1])
+
+
+@_fake("syevj")
+def _(M):
+    return M.new_empty(M.shape[0]), torch.empty_like(M)
+
+
 @_fake("lrp_conv_fwd")
 def _(x, wts, bias3, den_map, cout, ng, pool):
     B, cin, H, W = x.shape
@@ -143,6 +155,8 @@ drsa_objective = _ops.drsa_objective
 drsa_run = _ops.drsa_run
 polar = _ops.polar
 subspace_relevances = _ops.subspace_relevances
+prca_covariance = _ops.prca_covariance
+syevj = _ops.syevj
 lrp_conv_fwd = _ops.lrp_conv_fwd
 lrp_conv_bwd = _ops.lrp_conv_bwd
 lrp_linear_fwd = _ops.lrp_linear_fwd
@@ -174,5 +188,6 @@ def _(wav, n_fft, hop, n_mels, width, peak_norm):
     return wav.new_empty(wav.shape[0], 1, n_mels, width)
 
 
-__all__ = ["drsa_step", "drsa_objective", "drsa_run", "polar", "subspace_relevances", "lrp_conv_fwd", "lrp_conv_bwd",
+__all__ = ["drsa_step", "drsa_objective", "drsa_run", "polar", "subspace_relevances", "prca_covariance", "syevj",
+           "lrp_conv_fwd", "lrp_conv_bwd",
            "lrp_linear_fwd", "lrp_linear_bwd", "projection_fwd", "projection_bwd", "heatmap_sort", "logmel"]

@@ -9,6 +9,9 @@
                                                   layer in [1, 4, 7, 10, 13]
 * ``cf_random_subspace``           cpf.py:192-233 subspace heatmaps through a random orthogonal U
                                                   (ortho_group.rvs, column permutations compounding)
+* ``cf_prca_subspace``             (no reference)  subspace heatmaps through the class's PRCA basis
+                                                  (xai/drsa/prca.py): the data-driven baseline next
+                                                  to the random one
 * ``perform_cf``                   cpf.py:241-294 AUPC pickles per (K, layer)
 * ``sep_and_peak``                 cpf.py:297-371 separability / peakness per (K, layer), pickled
 * ``frob``                         cpf.py:374-395 mean pairwise Frobenius distance of concept maps
@@ -172,8 +175,38 @@ def cf_random_subspace(model, input_batch, name_map, layer_idx, dim, case=None, 
     return R if as_tensor else R.cpu().numpy()
 
 
+def cf_prca_subspace(model, input_batch, name_map, layer_idx, case=None, device=torch.device("cuda"),
+                     num_concepts: int = 4, as_tensor: bool = False):
+    """Subspace heatmaps [B, K, H, W] (numpy, or the device tensor with ``as_tensor``) of every class
+    block through that block's PRCA basis: (A, C) at ``layer_idx`` for the class at every location of
+    the block's samples, flattened to [b H W, d]; U = prca(A, C)[0], so concept 0 is the top-d/K
+    PRCA subspace."""
+    from ...zennit.composites import NameMapComposite
+    from ..drsa.preprocessing import preprocess_data
+    from ..drsa.prca import prca
+    if isinstance(input_batch, np.ndarray):
+        input_batch = torch.tensor(input_batch)
+    x = input_batch.to(device)
+    mapper = _mapper(case)
+    spc = x.size(0) // len(mapper)
+    composite = NameMapComposite(name_map=list(name_map))
+    heatmaps = []
+    for i, genre in enumerate(mapper):
+        xb = x[i * spc:(i + 1) * spc]
+        A, C = preprocess_data(model, xb, composite, layer_idx, mapper[genre], num_locations=None, device=device)
+        d = A.size(-1)
+        U = prca(A.reshape(-1, d).contiguous(), C.reshape(-1, d).contiguous())[0]
+        heatmaps.append(_subspace_heatmaps(model, xb, U, name_map, genre, num_concepts, layer_idx, device))
+    R = torch.cat(heatmaps, 0)
+    return R if as_tensor else R.cpu().numpy()
+
+
 def _subspace_source(model, x, name_map, layer_idx, k, dim, prefix, path, case, device):
-    """RU for one (K, layer): DRSA subspaces from ``path/{k}_concepts`` runs, or random ones."""
+    """RU for one (K, layer): DRSA subspaces from ``path/{k}_concepts`` runs, random ones (prefix
+    'random') or the PRCA basis (prefix 'prca')."""
+    if prefix == "prca":
+        return cf_prca_subspace(model, x, name_map, layer_idx, case=case, device=device, num_concepts=k,
+                                as_tensor=True)
     if prefix == "random":
         return cf_random_subspace(model, x, name_map, layer_idx, dim=dim, case=case, device=device, permutations=3,
                                   num_concepts=k, as_tensor=True)
@@ -193,7 +226,7 @@ def perform_cf(model, input_batch, name_map, out, path=None, layer_idcs=(1, 4, 7
     for k in num_concepts:
         for i, layer_idx in enumerate(layer_idcs):
             print(f"Performing concept patch flipping for {k} subspaces at layer {layer_idx}")
-            if prefix == "random":
+            if prefix in ("random", "prca"):
                 R = _subspace_source(model, x, name_map, layer_idx, k, dims[i], prefix, path, case, device)
                 aupc, _, _ = Flipper(perturbation_size=16, device=device)(_model_forward(model), x, R)
             else:

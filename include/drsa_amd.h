@@ -135,6 +135,40 @@ size_t drsa_amd_subspace_relevances_workspace_bytes(int64_t B, int64_t N, int d,
 int drsa_amd_subspace_relevances(const float* act, const float* ctx, int64_t B, int64_t N, int d, int K,
                                  const float* U, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Principal Relevant Component Analysis (csrc/prca.hip): the closed-form baseline of DRSA from the
+ * same paper.  The orthonormal U maximising tr(U^T M U), M = (A^T C + C^T A) / (2N), is the
+ * eigenvectors of the symmetric indefinite M by descending eigenvalue.  The reference has no PRCA;
+ * its habit for a d x d spectral step is a host float64 eigh (orthogonalize, drsa.py:201-221).
+ * Any 1 <= d <= 128 (DRSA_EUNSUPPORTED above) and N >= 1.  No call synchronises or allocates.
+ * ------------------------------------------------------------------------- */
+
+/* Bytes of device workspace drsa_amd_prca_partial needs for N rows (0: unsupported): one slab per
+ * leaf of the fixed row partition (min(256, ceil(N / 16)) leaves, as the DRSA gradient). */
+size_t drsa_amd_prca_workspace_bytes(int64_t N, int d);
+
+/* slab[d*d] = A^T C over this call's N rows, un-normalised (fp32 MFMA, each of A and C read once;
+ * deterministic: fixed leaves, fixed fold order, no atomics, so the bits depend neither on the
+ * device nor on the grid).  Slabs of row shards add up (the payload of an all-reduce). */
+int drsa_amd_prca_partial(const float* A, const float* C, int64_t N, int d, float* slab, void* ws, size_t ws_bytes,
+                          void* stream);
+
+/* M_out[i][j] = (slab[i][j] + slab[j][i]) / (2 N_total): symmetric bit for bit. */
+int drsa_amd_prca_finish(const float* slab, int64_t N_total, int d, float* M_out, void* stream);
+
+/* Eigen-decomposition of the symmetric M [d][d] (its upper triangle is read): w_out[d] descending
+ * (stable), V_out[d][d] with eigenvector k in column k, its entry of largest magnitude (lowest
+ * index on a tie) positive.  One workgroup, M in LDS, V in registers: cyclic two-sided Jacobi in
+ * round-robin order (ceil(d/2) disjoint Rutishauser rotations per step; a pair rests when |m_pq| <=
+ * 2^-24 max_k |m_kk|) until a sweep makes no rotation or 30 sweeps have run, so the call ends for
+ * any input; then V is re-orthogonalised by the Newton-Schulz polar of drsa_amd_polar and each w_k is
+ * the Rayleigh quotient v_k^T M v_k (float64 sum) against the input.  sweeps_out (nullable, device
+ * int) receives the sweep count.  The workspace (drsa_amd_syevj_workspace_bytes; 0: unsupported d)
+ * is the call's status block of four ints: {sweeps, 1 if the last sweep made no rotation, 0, 0}. */
+size_t drsa_amd_syevj_workspace_bytes(int d);
+int drsa_amd_syevj(const float* M, int d, float* w_out, float* V_out, int* sweeps_out, void* ws, size_t ws_bytes,
+                   void* stream);
+
 
 /* ------------------------------------------------------------------------- *
  * LRP engine (zennit 0.5.1 rules over the VGG-type CNN; cxai/xai/explain).
