@@ -310,6 +310,7 @@ int drsa_amd_first_layer_bwd(const float* g, const uint8_t* amax, const float* w
   DRSA_REQUIRE((int64_t)C * H * W < ((int64_t)1 << 31), "first_layer_bwd: one sample's C x H x W must stay below 2^31");
   if (amax) {
     DRSA_REQUIRE(H % 2 == 0 && W % 4 == 0, "first_layer_bwd: pooled path needs even H and W % 4 == 0");
+    DRSA_REQUIRE(((uintptr_t)out & 15) == 0, "first_layer_bwd: pooled path stores float4: out must be 16-byte aligned");
     const int H2 = H / 2, W2 = W / 2;
     const dim3 grid(((H2 + FQ_Y - 1) / FQ_Y) * ((W2 + FQ_X - 1) / FQ_X), Bq);
     constexpr size_t lds = sizeof(float) * FQ_PY * FQ_PX;
@@ -318,7 +319,9 @@ int drsa_amd_first_layer_bwd(const float* g, const uint8_t* amax, const float* w
     hipLaunchKernelGGL(kf, grid, dim3(256), lds, (hipStream_t)stream, g, amax, w2f, out, C, H, W, clones);
   } else {
     const dim3 grid(((H + FL_TH - 1) / FL_TH) * ((W + FL_TW - 1) / FL_TW), Bq);
-    if (W % 4 == 0)
+    // float4 loads of g rows: every row starts a multiple of 4 floats from the base (W % 4 == 0), so
+    // the base decides the alignment; any other base takes the scalar loads (same chain, same values)
+    if (W % 4 == 0 && ((uintptr_t)g & 15) == 0)
       hipLaunchKernelGGL(first_layer_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, g, w2f, out, C, H, W);
     else
       hipLaunchKernelGGL(first_layer_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, g, w2f, out, C, H, W);

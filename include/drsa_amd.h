@@ -361,7 +361,9 @@ int drsa_amd_ab_split(const float* g, const float* den_p, const float* den_n, fl
 int drsa_amd_ab_combine(const float* pos, const float* neg, float alpha, float beta, const float* x, const float* den,
                         float* out, int Bq, int clones, int64_t n, int post, float eps, void* stream);
 
-/* First-layer (one input channel) WSquare / Flat backward: R = J^T_{W2} g. */
+/* First-layer (one input channel) WSquare / Flat backward: R = J^T_{W2} g.  amax != NULL: g is the
+ * pooled relevance (even H, W % 4 == 0, out 16-byte aligned).  amax == NULL: g is dense, any H, W and
+ * alignment (float4 loads when W % 4 == 0 and g is 16-byte aligned, scalar loads otherwise; same values). */
 int drsa_amd_first_layer_bwd(const float* g, const uint8_t* amax, const float* w2, float* out, int Bq, int clones,
                              int C, int H, int W, void* stream);
 

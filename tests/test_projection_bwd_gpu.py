@@ -1,5 +1,5 @@
 """drsa_amd_projection_bwd: the recompute path (h and a' rebuilt from a, the engine default) against
-the stored-buffer path, bitwise, over d (16 / 64 / 128: the register and the L1 a / den paths; 12 /
+the stored-buffer path, bitwise, over d (16 / 32 / 64 / 128: the register and the L1 a / den paths; 12 /
 24 / 100: the zero-padded embedding in the next wider kernel), K (d_k = 4, 8, 16, 25, 32: the generic
 clone loop and its d_k = 16 form), the tile shapes (8 x 8, 4 x 16, 2 x 32 pixels), fan-out modes, the
 pooled and the dense relevance input, and with and without the lower layer's denominator (den = NULL
@@ -82,7 +82,7 @@ def _recompute_equals_stored(D, K, pool, has_den, fanout, H, W):
 
 
 # d = DP (no padding code) and d < DP (12 -> 16, 24 -> 32, 100 -> 128: the VGGish width, d_k = 25)
-@pytest.mark.parametrize("D,K", [(16, 4), (64, 4), (64, 8), (64, 2), (128, 4), (12, 3), (24, 3), (100, 4)])
+@pytest.mark.parametrize("D,K", [(16, 4), (32, 4), (64, 4), (64, 8), (64, 2), (128, 4), (12, 3), (24, 3), (100, 4)])
 @pytest.mark.parametrize("pool", [0, 1])
 @pytest.mark.parametrize("has_den", [True, False])
 @pytest.mark.parametrize("fanout", [0, 1, 2])
