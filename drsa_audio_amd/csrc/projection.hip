@@ -353,15 +353,23 @@ __global__ __launch_bounds__(256) void projection_bwd_kernel(
 // tiles per workgroup (U staged once): 2 / 4 / 8 -> 0.332-0.334 / 0.337-0.338 / 0.378-0.385 ms in the step
 constexpr int PT_RC = 2;
 
-// 3 waves/SIMD at DP <= 64: the a' pass below is a separate GEMM so that its accumulators fit there
-template <int DP, bool PAD>
+// 3 waves/SIMD at DP <= 64: the a' pass below is a separate GEMM so that its accumulators fit there.
+// SPARSE (a 2x2 max-pool follows the projection: gp is pooled, amax selects) and DEN (the lower
+// layer's denominator is given) are compile-time: tested per element at run time they cost the
+// DP = 64 kernel 48 of its 71 branches.
+template <int DP, bool PAD, bool SPARSE, bool DEN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DP <= 64 ? 3 : 1))) void projection_bwd_rc_kernel(
     const float* __restrict__ gp, const uint8_t* __restrict__ amax, const float* __restrict__ a,
     const float* __restrict__ den, const float* __restrict__ U, const float* __restrict__ Pm, float* __restrict__ G,
-    int d_in, int H, int W, int K, float eps_proj, float eps_den, int sparse, int has_den, int fanout) {
+    int d_in, int H, int W, int K, float eps_proj, float eps_den, int fanout) {
   const int d = PAD ? d_in : DP;
   constexpr int P = 64, LD = DP + 1, PW = 16, NB = DP / 16;
   constexpr bool PF = DP <= 64;   // keep a / den of the output rows in registers
+  // the tile's relevance gather (gp, and amax when SPARSE) as one batch of loads in flight across
+  // the a' GEMM: 162 of the 168 VGPRs of 3 waves/SIMD at d = DP = 64.  Where its 2 NB * 4
+  // registers do not fit without (more) scratch -- DP = 128, and d < DP = 64 with its padding
+  // selects -- the gather stays per element, after that GEMM.
+  constexpr bool GATHER = DP <= 32 || (DP == 64 && !PAD);
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
   float* Us = sm;                                   // [DP][LD]
@@ -373,12 +381,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DP <= 64 ? 
   // per-sample bases (uniform, 64-bit) + 32-bit per-lane offsets: saddr + voffset addressing
   // instead of a 64-bit multiply-add per element (the host keeps d * H * W < 2^31)
   const float* __restrict__ a_b = a + (size_t)b * d * HW;
-  const float* __restrict__ den_b = has_den ? den + (size_t)b * d * HW : a_b;
-  const float* __restrict__ gp_b = gp + (size_t)b * d * (sparse ? H2 * W2 : HW);
-  const uint8_t* __restrict__ am_b = sparse ? amax + (size_t)b * d * H2 * W2 : nullptr;
+  const float* __restrict__ den_b = DEN ? den + (size_t)b * d * HW : a_b;
+  const float* __restrict__ gp_b = gp + (size_t)b * d * (SPARSE ? H2 * W2 : HW);
+  const uint8_t* __restrict__ am_b = SPARSE ? amax + (size_t)b * d * H2 * W2 : nullptr;
   const int dk = d / K, d4 = (d + 3) & ~3;
-  // fanout 1: K+1 clones (standard + K subspaces); 2: the K subspace clones only; 0: replicated rows
+  // fanout 1: K+1 clones (standard + K subspaces); 2: the K subspace clones only; 0: replicated rows.
+  // Clone qi masks subspace q0 + qi (0 = none) and writes output row orow0 + qi.
   const int nq = fanout == 1 ? (K + 1) : fanout == 2 ? K : 1;
+  const int q0 = fanout == 1 ? 0 : fanout == 2 ? 1 : b % (K + 1);
+  const size_t orow0 = fanout ? (size_t)b * nq : (size_t)b;
   const int pc = lane & 15, rg = lane >> 4;         // pixel column / row group of the MFMA layouts
   stage_u_padded<DP>(Us, U, d, tid);
   __syncthreads();
@@ -390,6 +401,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DP <= 64 ? 
     const int py = y0 + pl / TW, px = x0 + pl % TW;
     const int pixl = py * W + px;
     const int cell = (py >> 1) * W2 + (px >> 1);
+    const int sub = ((py & 1) << 1) | (px & 1);       // this pixel's position in its pool cell
     // a (and den) at rows c = i*16 + 4 rg + r: the output layout of every GEMM below
     float av[NB * 4], dv[PF ? NB * 4 : 1];
 #pragma unroll
@@ -401,7 +413,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DP <= 64 ? 
         const int os = (ok ? c : 0) * HW + pixl;
         const float aa = a_b[os];
         av[i * 4 + r] = ok ? aa : 0.f;
-        if constexpr (PF) dv[i * 4 + r] = has_den ? den_b[os] : 1.f;
+        if constexpr (PF) dv[i * 4 + r] = DEN ? den_b[os] : 1.f;
       }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -431,6 +443,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DP <= 64 ? 
     // folded into the h GEMM above, the second accumulator set spills at 3 waves/SIMD);
     // g1 = R_a' / stab(a')  -> region A (in place of a; a stays in registers)
     {
+      // R_a' of the lane's NB * 4 (channel, pixel) elements: every load is issued here,
+      // unconditionally (rows past d read row 0), ahead of the GEMM; the argmax select and the
+      // divisions follow it, with no wait on memory between them
+      float gv[GATHER ? NB * 4 : 1];
+      int am[GATHER && SPARSE ? NB * 4 : 1];
+      if constexpr (GATHER) {
+#pragma unroll
+        for (int i = 0; i < NB * 4; ++i) {
+          const int c = (i >> 2) * 16 + rg * 4 + (i & 3);
+          const int cc = c < d ? c : 0;
+          gv[i] = gp_b[SPARSE ? cc * H2 * W2 + cell : cc * HW + pixl];
+          if constexpr (SPARSE) am[i] = am_b[cc * H2 * W2 + cell];
+        }
+      }
       f32x4 acc[NB];
 #pragma unroll
       for (int cb = 0; cb < NB; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -450,10 +476,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DP <= 64 ? 
           const bool ok = c < d;
           const int cc = ok ? c : 0;
           float R;
-          if (sparse) {
+          if constexpr (GATHER) {
+            R = SPARSE ? ((am[cb * 4 + r] == sub) ? gv[cb * 4 + r] : 0.f) : gv[cb * 4 + r];
+          } else if constexpr (SPARSE) {
             const int q = cc * H2 * W2 + cell;
-            const float gv = gp_b[q];   // unconditional load, then the argmax select
-            R = (am_b[q] == (((py & 1) << 1) | (px & 1))) ? gv : 0.f;
+            const float g = gp_b[q];   // unconditional load, then the argmax select
+            R = (am_b[q] == sub) ? g : 0.f;
           } else {
             R = gp_b[cc * HW + pixl];
           }
@@ -489,13 +517,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DP <= 64 ? 
     // quotient is x / 1 = x exactly), so the clone epilogue below is branch-free
     if constexpr (PF) {
 #pragma unroll
-      for (int i = 0; i < NB * 4; ++i) dv[i] = has_den ? stab(dv[i], eps_den) : 1.f;
+      for (int i = 0; i < NB * 4; ++i) dv[i] = DEN ? stab(dv[i], eps_den) : 1.f;
     }
     for (int qi = 0; qi < nq; ++qi) {
-      const int q = fanout == 1 ? qi : fanout == 2 ? qi + 1 : b % (K + 1);
+      const int q = q0 + qi;
       const int j0 = q == 0 ? 0 : (q - 1) * dk, j1 = q == 0 ? d : q * dk;
-      const size_t orow = fanout ? (size_t)b * nq + qi : (size_t)b;
-      float* __restrict__ G_q = G + orow * d * HW;
+      float* __restrict__ G_q = G + (orow0 + qi) * d * HW;
       f32x4 acc[NB];
 #pragma unroll
       for (int cb = 0; cb < NB; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -542,7 +569,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DP <= 64 ? 
             sd = dv[cb * 4 + r];
           } else {
             const float dx = den_b[os];   // den_b is a valid row (a) without den
-            sd = has_den ? stab(dx, eps_den) : 1.f;
+            sd = DEN ? stab(dx, eps_den) : 1.f;
           }
           const float qd = div_nb(ax * acc[cb][r], sd);   // every lane, then the select
           const float gq = (ax > 0.f) ? qd : 0.f;
@@ -642,9 +669,13 @@ int drsa_amd_projection_bwd(const float* gp, const uint8_t* amax, const float* a
     return with_flag(D != DP, [&](auto pad) -> int {
       constexpr bool PAD = decltype(pad)::value;
       if (recompute)
-        return launch_proj(projection_bwd_rc_kernel<DP, PAD>, dim3((tiles + PT_RC - 1) / PT_RC, B),
-                           proj_bwd_rc_lds<DP>(), s, gp, amax, a, den, U, P, G, D, H, W, K, eps_proj, eps_den, sparse,
-                           has_den, fanout);
+        return with_flag(sparse, [&](auto sp) -> int {
+          return with_flag(has_den, [&](auto dn) -> int {
+            return launch_proj(projection_bwd_rc_kernel<DP, PAD, decltype(sp)::value, decltype(dn)::value>,
+                               dim3((tiles + PT_RC - 1) / PT_RC, B), proj_bwd_rc_lds<DP>(), s, gp, amax, a, den, U, P,
+                               G, D, H, W, K, eps_proj, eps_den, fanout);
+          });
+        });
       return launch_proj(projection_bwd_kernel<DP, PAD>, dim3((tiles + PT_BWD - 1) / PT_BWD, B), proj_bwd_lds<DP>(), s,
                          gp, amax, ap, h, a, den, U, G, D, H, W, K, eps_proj, eps_den, sparse, has_den, fanout);
     });
