@@ -1512,8 +1512,12 @@ int check_problem(const char* who, Geom& g, int d, int K, int64_t N, unsigned ne
   DRSA_REQUIRE(g.ok, "%s: unsupported d=%d K=%d (need d <= 128, K | d, padded concept width <= 64 and "
                "K * padded width <= 128)", who, d, K);
   DRSA_REQUIRE(N > 0 || (N == 0 && (need & kEmptyOk)), "%s: N must be %s 0", who, (need & kEmptyOk) ? ">=" : ">");
-  DRSA_REQUIRE(!(need & kDtype) || a.dtype == 0 || ((a.dtype == 1 || a.dtype == 2) && g.DP >= 32),
-               "%s: dtype must be 0 (fp32) or 1/2 (bf16/fp16, padded d >= 32)", who);
+  DRSA_REQUIRE(!(need & kDtype) || (a.dtype >= 0 && a.dtype <= 2), "%s: dtype must be 0 (fp32) or 1/2 (bf16/fp16)",
+               who);
+  if ((need & kDtype) && a.dtype && g.DP < 32) {   // a valid request with no kernel: the 16-bit MFMA tiles are 32 deep
+    drsa::set_error("%s: unsupported d=%d K=%d for 16-bit A, C (needs padded d >= 32)", who, d, K);
+    return DRSA_EUNSUPPORTED;
+  }
   DRSA_REQUIRE(!(need & kNoAlias) || a.U != a.U_out, "%s: U and U_out must not alias", who);
   if (N == 0) return DRSA_OK;
   DRSA_REQUIRE(!(need & kWs) || (a.ws && a.ws_size >= ws_bytes(N, g)), "%s: workspace too small", who);

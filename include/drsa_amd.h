@@ -399,7 +399,8 @@ typedef struct drsa_amd_problem {
 
 /* drsa_amd_drsa_partial with A, C stored as bf16 (C5: bf16 input; the U-projection GEMM runs on
  * bf16 MFMA with fp32 accumulation, U rounded to bf16 per step; the gradient GEMM and every
- * reduction stay fp32).  No reference bf16 path exists: its tolerance is looser (tests). */
+ * reduction stay fp32).  No reference bf16 path exists: its tolerance is looser (tests).
+ * Padded d >= 32 (the 16-bit MFMA tiles are 32 deep): DRSA_EUNSUPPORTED at padded d = 16. */
 int drsa_amd_drsa_partial_bf16(const uint16_t* A, const uint16_t* C, int64_t N, int d, int K, const float* U,
                                float* gs_out, void* ws, size_t ws_size, void* stream);
 /* The same with A, C as fp16 (C5's "fp16 MFMA projection": v_mfma_f32_16x16x32_f16, U rounded to
