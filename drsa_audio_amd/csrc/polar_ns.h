@@ -1,4 +1,5 @@
-// Polar factor by Newton-Schulz in one workgroup (shared by drsa_step.hip and scripts/probe_ns.hip).
+// Polar factor by Newton-Schulz in one workgroup (shared by drsa_finish.h, drsa_coop.h and
+// scripts/probe_ns.hip).
 //   X0 = a V (a from the first Gram matrix: sqrt(DP / tr) unless that overshoots the inf-norm);
 //   P = X^T X (upper 32x32 block triangle, mirrored), T = 1.5 I - 0.5 P, X <- X T until max|P - I| < tol
 //   or until the next update provably lands there / rounding has become the floor.

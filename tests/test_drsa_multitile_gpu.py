@@ -66,6 +66,7 @@ def test_tile_counts():
     assert [tiles(N, d, K) for d, K, N, _ in PARTIAL] == [[1, 2], [1, 2], [2, 3], [1, 2], [1, 2], [2, 3]]
     assert tiles(32803, 32, 4) == [1, 2] and tiles(300, 32, 4) == [1] and tiles(500, 66, 2) == [1]
     assert tiles(41003, 100, 4) == [2, 3]
+    assert sr.geom(42, 3)[1:3] == (16, 64) and tiles(32803, 42, 3) == [1, 2] and tiles(300, 42, 3) == [1]
 
 
 @pytest.mark.parametrize("d,K,N,dt", [(d, K, N, dt) for d, K, N, dts in PARTIAL for dt in dts])
@@ -97,6 +98,9 @@ def test_multitile_step_matches_reference_finish(N, d, K):
 
 BATCHED = {"grouped": [(32803, 32, 4), (300, 32, 4)],          # drsa_partial_grouped_kernel: 1-2 tiles | 1
            "grouped128": [(20603, 100, 4), (41003, 100, 4)],   # the same at DP = 128: 1-2 tiles | 2-3
+           # the grouped kernel with scalar staging (d % 4 != 0; DP = 64, DKp = 16): 1-2 tiles | 19 one-block
+           # leaves in 3 groups, the last leaf 12 rows
+           "grouped_scalar": [(32803, 42, 3), (300, 42, 3)],
            "leafwise": [(20603, 66, 2), (500, 66, 2)]}         # drsa_partial_leaf_batched_kernel, scalar staging
 
 
