@@ -1,7 +1,8 @@
-// Host dispatch of the 3x3 conv kernels (kernel: lrp_conv_kernel.h; instantiations: conv_*.hip).
+// Host dispatch of the 3x3 conv kernels (kernel: lrp_conv_kernel.h; instantiations: conv_*.hip
+// through lrp_conv_inst.h).  Only the tables and the configuration are seen here, not the kernel.
 #include "common.h"
 #include "lrp_conv.h"
-#include "lrp_conv_kernel.h"
+#include "lrp_conv_table.h"
 
 #include <stdlib.h>
 
@@ -28,36 +29,15 @@ const drsa_conv::Table* kTables[] = {DRSA_CONV_TABLES(DRSA_CONV_ADDRESS)};
 
 int pad32(int c) { return (c + 31) / 32 * 32; }
 
-// Tile shape per direction, channel width and map width (measured choices; variant builds change
-// them with -D, scripts/build_variant.py):
-// * W >= 32: 8 x 32 tiles, except 8 x 16 for the fp32 forward into 64 channels (half the
-//   accumulators: 2 waves/SIMD instead of 1; GTZAN conv_fwd:features.6 0.391 -> 0.356 ms, VGGish
-//   features.3 1.43 -> 1.36 ms), the fp32 backward into 64 channels (the 8 x 32 tile with 16-channel
-//   chunks spills 91-115 VGPRs) and into 128 channels (VGGish features.17: the 8 x 32 tile spills
-//   358-435 VGPRs; 0.291 -> 0.101 ms); the fp32 forward into 128 channels on 8 x 8 tiles (4 times the
-//   workgroups at 3 waves/SIMD instead of 1: VGGish conv_fwd:features.17 0.318 -> 0.175 ms, .14 0.168
-//   -> 0.100 ms, fp32 standard LRP 7.6k -> 8.0k samples/s; 8 x 16: 0.189 / 0.101 ms);
-// * 8 < W < 32: 8 x 8 tiles (more workgroups for the small layers: conv_fwd:features.9 0.287 -> 0.266
-//   ms, conv_bwd 0.218 -> 0.214 at B = 512);  W <= 8: 8 x 8.
-// Measured slower and dropped: 16-row tiles, 32-channel fp32 forwards / backwards on 8 x 16 tiles.
-#ifndef DRSA_CONV_FWD128_TW
-#define DRSA_CONV_FWD128_TW 8    // fp32 forward into 128 channels at W >= 32: tile width (32, 16 or 8)
-#endif
+// The tables hold, per kernel set, the one tile of each width class (the tile rule:
+// lrp_conv_config.h wide_tile_w()), so the lookup only picks the class of W.
 const Entry* find(int cin_p, int cout_p, int W, int ng, int amode, int epi, int et = 0, int pw = 2) {
-  int th = 8, tw, mw;
-  const bool fwd_t16 = epi != EPI_BWD && et == 0 && cout_p == 64;
-  const bool bwd_t16 = epi == EPI_BWD && et == 0 && ((cout_p == 64 && cin_p <= 128) || cout_p == 128);
-  if (W >= 32 && epi != EPI_BWD && et == 0 && cout_p == 128 && DRSA_CONV_FWD128_TW != 32) {
-    tw = DRSA_CONV_FWD128_TW;
-    mw = tw == 8 ? 4 : 8;
-  } else if (W >= 32 && (fwd_t16 || bwd_t16)) { tw = 16; mw = 8; }
-  else if (W >= 32) { tw = 32; mw = 8; }
-  else { tw = 8; mw = 4; }
+  const int wide = W >= kWideW;
   for (const drsa_conv::Table* t : kTables)
     for (int i = 0; i < t->n; ++i) {
       const Entry& e = t->entries[i];
-      if (e.cin_p == cin_p && e.cout_p == cout_p && e.th == th && e.tw == tw && e.mw == mw && e.ng == ng &&
-          e.amode == amode && e.epi == epi && e.et == et && e.pw == pw)
+      if (e.cin_p == cin_p && e.cout_p == cout_p && e.ng == ng && e.amode == amode && e.epi == epi && e.et == et &&
+          e.pw == pw && e.wide == wide)
         return &e;
     }
   return nullptr;

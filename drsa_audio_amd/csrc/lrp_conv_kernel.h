@@ -23,60 +23,22 @@
 // channels staged in LDS with the halo; weights [k][co] staged next to them).  Every output
 // is one k-ordered fp32 fma chain (MFMA f32 semantics), independent of the chunking, which
 // is what oracle/lrp_exact.c reproduces bit for bit.
+//
+// This file: the kernel (prologue, chunk loop, epilogues).  Its parts: lrp_conv_config.h (build
+// knobs, tile rule, ConvCfg), lrp_conv_stage.h / lrp_conv_stage_bf.h (fp32 / bf16 staging),
+// lrp_conv_mfma.h (the MFMA loops over a staged chunk); lrp_conv_inst.h instantiates it into the
+// tables of lrp_conv_table.h.
 #pragma once
 #include "common.h"
 #include "lrp_conv.h"
+#include "lrp_conv_config.h"
+#include "lrp_conv_mfma.h"
+#include "lrp_conv_stage.h"
+#include "lrp_conv_stage_bf.h"
 
 #include <type_traits>
 
-#ifndef DRSA_CONV_PD_BWD
-#define DRSA_CONV_PD_BWD 2
-#endif
-#ifndef DRSA_CONV_BWD_ES
-#define DRSA_CONV_BWD_ES 1
-#endif
-#ifndef DRSA_CONV_BWD_WPE
-#define DRSA_CONV_BWD_WPE 3
-#endif
-// small-chunk rule backward (SMALL_BWD: GTZAN conv_bwd:features.3 / .6): its MFMA operand ring is
-// pinned (a sched_barrier per k-step keeps step k + PD's LDS reads ahead of step k's MFMAs; the
-// scheduler otherwise sinks each read next to its MFMA behind an lgkmcnt(0) wait) at distance 3.
-// Measured in the step (gpurun_out/r6j, r6k): features.3 1.373-1.383 -> 1.335 ms, .6 0.632 ->
-// 0.613; pinning the forwards or the wider backwards as well made them 2-6 % slower.
-#ifndef DRSA_CONV_PIN_SMALL
-#define DRSA_CONV_PIN_SMALL 1
-#endif
-#ifndef DRSA_CONV_PD_SMALL
-#define DRSA_CONV_PD_SMALL 3
-#endif
-#ifndef DRSA_CONV_SMALL_WPE
-#define DRSA_CONV_SMALL_WPE 4      // small-chunk backward: 4 workgroups (16 waves) per CU
-#endif
-#ifndef DRSA_CONV_SMALL_ES
-#define DRSA_CONV_SMALL_ES 2       // small-chunk backward: epilogue in 2 channel passes of 16
-#endif
-#ifndef DRSA_CONV_PRE_D
-#define DRSA_CONV_PRE_D 0
-#endif
-#ifndef DRSA_CONV_PRE_N
-#define DRSA_CONV_PRE_N 64
-#endif
-#ifndef DRSA_CONV_BF_WPE
-#define DRSA_CONV_BF_WPE 2
-#endif
-#ifndef DRSA_CONV_FWD_WPE_128
-#define DRSA_CONV_FWD_WPE_128 3    // 8 x 8-tile forwards into 128 channels with 4-channel chunks: 2 -> 3 waves/SIMD
-#endif
-#ifndef DRSA_CONV_FWD_WPE_WIDE
-#define DRSA_CONV_FWD_WPE_WIDE 3   // forwards into 64 channels (CIC <= 8, NG <= 2): 1 -> 3 conv_fwd:features.6 0.361 -> 0.343 ms
-#endif
-#ifndef DRSA_CONV_FWD_WPE
-#define DRSA_CONV_FWD_WPE 3
-#endif
-
 namespace drsa_conv {
-
-constexpr int kThreads = 256;
 
 // diagnostic build only (-DDRSA_CONV_STAMP, scripts/probe_conv_phases.py): phase times of every
 // workgroup of the 32 -> 32 pool-sparse backward (GTZAN conv_bwd:features.3) into a buffer of their
@@ -87,636 +49,6 @@ static __device__ unsigned long long* g_conv_stamps;
 
 // bias3 of a forward call without bias ([3][COUT], COUT <= 128)
 __device__ const float g_zero_bias3[3 * 128] = {};
-
-template <int V, int M>
-constexpr int round_up() { return (V + M - 1) / M * M; }
-
-// halo row stride: the 32 lanes of one ds_read_b32 group read a (16/MW x 2) grid of
-// MW*2-pixel runs; RS = 16 (mod 32) for 2 rows x 16, RS = 8 (mod 32) for 4 rows x 8 puts the
-// runs on disjoint banks.
-constexpr int halo_stride(int hx, int mw) {
-  int r = hx;
-  const int want = (mw == 8) ? 16 : 8;
-  while (r % 32 != want) ++r;
-  return r;
-}
-
-enum AMode { A_DENSE = 0, A_POOLSPARSE = 1 };
-enum Epi { EPI_FWD_POOL = 0, EPI_FWD_RELU = 1, EPI_BWD = 2 };
-
-// halo column c (pixel tx0 - 1 + c) lives at LDS column c + XO, so the tile interior starts
-// 16-byte aligned (float4 staging stores) and pool cells cover aligned float2 pairs.
-constexpr int XO = 3;
-
-// bf16 halo row stride in 16-byte pixels: >= hx and 8 (mod 16), so the two rows of a 2x2-window
-// run of 16 lanes land on disjoint bank halves (ds_read_b128)
-constexpr int bf_stride(int hx) {
-  int r = hx;
-  while (r % 16 != 8) ++r;
-  return r;
-}
-
-// ET (element type of the MFMA operands): 0 = fp32 (v_mfma_f32_32x32x2_f32, the exact k-ordered
-// chain), 1 = bf16 (v_mfma_f32_32x32x16_bf16, forward only: conv inputs and weights rounded to
-// bf16 when staged, fp32 accumulation, fp32 outputs).  The bf16 chunk is 16 input channels = one
-// tap per MFMA (k = tap * 16 + ci); its halo is pixel-major, 8 channels per 16-byte pixel slot.
-template <int CIN, int COUT, int TH, int TW, int MW, int CIC, int NG, int AMODE, int EPI, int ET = 0, int PW = 2>
-struct ConvCfg {
-  static constexpr int CIN_ = CIN, COUT_ = COUT, TH_ = TH, TW_ = TW, MW_ = MW, CIC_ = CIC, NG_ = NG;
-  static constexpr int AMODE_ = AMODE, EPI_ = EPI;
-  static constexpr bool BF = ET == 1;
-  static constexpr int HY = TH + 2, HX = TW + 2;
-  static constexpr int HXB = bf_stride(HX);
-  // bf16 staging: halo [2 channel halves][HY][HXB] x 16 B, weights [NG][9 taps][2][COUT] x 16 B
-  static constexpr size_t bf_halo_floats = (size_t)2 * HY * HXB * 4;
-  static constexpr size_t bf_w_floats = (size_t)NG * 9 * 2 * COUT * 4;
-  static constexpr int RS = halo_stride(HX + XO, MW);
-  static constexpr int PLANE_RAW = HY * RS;
-  static constexpr int PLANE = PLANE_RAW + ((PLANE_RAW % 32) == 0 ? 4 : 0);
-  // M-tile = the 32 pixels of one MFMA B operand: window-major 2x2 pool windows (MTH = 16/MW rows
-  // x 2*MW)
-  static constexpr int MTW = 2 * MW;
-  static constexpr int MTH = 32 / MTW;
-  static constexpr int MTX = TW / MTW;     // M-tiles per tile row
-  static constexpr int MT = (TH / MTH) * MTX;
-  static constexpr int NT = COUT / 32;
-  static constexpr int WM = MT >= 4 ? 4 : MT;
-  static constexpr int WN = (4 / WM) < NT ? (4 / WM) : NT;   // waves >= WM*WN idle (tiny layers)
-  static constexpr int MPW = MT / WM;      // m-tiles per wave
-  static constexpr int NPW = NT / WN;      // n-tiles per wave
-  static constexpr int KC = 9 * CIC;
-  static constexpr int KCP = round_up<KC, 2>();
-  static constexpr int NCHUNK = CIN / CIC;
-  static constexpr int TWP = (TW == 32) ? 48 : TW;          // epilogue tile row stride (conflict-free writes)
-  // backward epilogue in ES channel passes (halves the epilogue LDS and registers; WN == 1 only)
-  // small-chunk rule backward (CIC <= 8, 32 output channels): 24.6 KB LDS and <= 128 VGPRs, so
-  // 4 workgroups (16 waves) per CU
-  static constexpr bool SMALL_BWD = EPI == EPI_BWD && NG == 1 && CIC <= 8 && COUT <= 32;
-  static constexpr int ES = (EPI == EPI_BWD && WN == 1) ? (SMALL_BWD ? DRSA_CONV_SMALL_ES : DRSA_CONV_BWD_ES) : 1;
-  static constexpr int TCH = WN * 32 / ES;                     // channels staged per epilogue pass
-  static constexpr size_t staging_floats =
-      BF ? bf_halo_floats + bf_w_floats : (size_t)CIC * PLANE + (size_t)NG * KCP * COUT;
-  static constexpr size_t epi_floats = (size_t)TCH * TH * TWP;
-  static constexpr size_t lds_floats = staging_floats > epi_floats ? staging_floats : epi_floats;
-  // minimum waves per SIMD the register allocation must allow (1 block = 1 wave per SIMD)
-  static constexpr int WPE = BF ? (COUT <= 64 ? DRSA_CONV_BF_WPE : 1)
-                             : (EPI == EPI_BWD && NG == 1) ? (SMALL_BWD ? DRSA_CONV_SMALL_WPE : DRSA_CONV_BWD_WPE)
-                             : (EPI != EPI_BWD && CIC <= 8 && COUT <= 32 && NG <= 2 ? DRSA_CONV_FWD_WPE
-                                : EPI != EPI_BWD && CIC <= 8 && NG <= 2 && COUT == 64 ? DRSA_CONV_FWD_WPE_WIDE
-                                : EPI != EPI_BWD && CIC <= 4 && NG <= 2 && COUT == 128 && TW == 8 ? DRSA_CONV_FWD_WPE_128 : 1);
-  // operand prefetch distance of the MFMA loop (k-steps)
-  static constexpr bool PIN = SMALL_BWD && DRSA_CONV_PIN_SMALL;
-  static constexpr int PD = PIN ? DRSA_CONV_PD_SMALL : DRSA_CONV_PD_BWD > 0 && EPI >= EPI_BWD ? DRSA_CONV_PD_BWD : 1;
-  static_assert(TH % MTH == 0 && TW % MTW == 0, "tile must be a multiple of the M-tile");
-  static_assert(COUT % 32 == 0, "COUT must be padded to 32");
-  static_assert(CIN % CIC == 0, "CIN must be a multiple of the chunk");
-  static_assert(MT % WM == 0 && NT % WN == 0 && WM * WN <= 4, "wave split");
-  static_assert(!BF || (CIC == 16 && (EPI < EPI_BWD ? AMODE == A_DENSE : EPI == EPI_BWD)),
-                "bf16: 16-channel chunks; dense forward, or the per-clone backward (dense or pool-sparse g)");
-  static_assert(PW == 2 || (PW == 4 && (EPI == EPI_FWD_POOL || (EPI == EPI_BWD && AMODE == A_POOLSPARSE &&
-                                                                  (ET == 1 || TW % 16 == 0)))),
-                "2x4 pool windows: the forward pool epilogue, or the backward's pool-sparse staging (fp32: "
-                "tiles of whole float4 cell groups)");
-  static constexpr int PW_ = PW;
-};
-
-// ---- staging of one input-channel chunk: registers <- global (load), LDS <- registers
-//      (store), split so that the loads of the next chunk can be issued before the MFMA loop
-//      of the current one.  NT_ threads take part (tid in [0, NT_)). ----
-template <class Cfg, int NT_ = kThreads>
-struct Stager {
-  static constexpr int CIN = Cfg::CIN_, COUT = Cfg::COUT_, TH = Cfg::TH_, TW = Cfg::TW_, CIC = Cfg::CIC_;
-  static constexpr int NG = Cfg::NG_, HY = Cfg::HY, HX = Cfg::HX, RS = Cfg::RS, PLANE = Cfg::PLANE;
-  static constexpr int KC = Cfg::KC, KCP = Cfg::KCP;
-  static constexpr bool DENSE = Cfg::AMODE_ == A_DENSE;
-  // dense halo: interior rows of TW/4 float4 + the two halo columns
-  static constexpr int Q4 = TW / 4, DROWS = CIC * HY;
-  static constexpr int DI = (DROWS * Q4 + NT_ - 1) / NT_, DH = (DROWS * 2 + NT_ - 1) / NT_;
-  // pool-sparse cells: interior rows of TW/8 float4 (4 cells) + the two halo cell columns
-  static constexpr int CY = TH / 2 + 2, CX = TW / 2 + 2, Q8 = TW / 8 > 0 ? TW / 8 : 1, SROWS = CIC * CY;
-  static constexpr int SI = (SROWS * Q8 + NT_ - 1) / NT_, SH = (SROWS * 2 + NT_ - 1) / NT_;
-  // P4: 2 x 4 cells (VGGish's (2,4) pool folded into the staging): interior rows of TW/16 float4
-  // (4 cells = 16 pixels each) + the two halo cells, which reach 1 pixel into the halo each
-  static constexpr bool P4 = !DENSE && Cfg::PW_ == 4;
-  static constexpr int Q16 = TW / 16 > 0 ? TW / 16 : 1;
-  static constexpr int SI4 = (SROWS * Q16 + NT_ - 1) / NT_;
-  static constexpr int NI = DENSE ? DI : P4 ? SI4 : SI, NH = DENSE ? DH : SH;
-  static constexpr int NWV = NG * KCP * (COUT / 4), WIT = (NWV + NT_ - 1) / NT_;
-  float4 st_i[NI];
-  uint32_t st_ia[DENSE ? 1 : NI];
-  float st_h[NH];
-  int st_ha[DENSE ? 1 : NH];
-  float4 st_w[WIT];
-
-  // Loads are unconditional from a clamped (always valid) address and masked afterwards, so
-  // the compiler issues them back to back without exec branches or per-load waits.
-  __device__ __forceinline__ void load(const ConvArgs& a, int c0, int tid, int ty0, int tx0, int bq, int bs) {
-    const int H = a.H, W = a.W, H2 = H >> 1, W2 = W >> 1;
-    // per-sample bases (uniform) + 32-bit per-lane offsets: saddr + voffset loads instead of a
-    // 64-bit multiply-add per element (the host keeps one sample's cin x H x W below 2^31)
-    const int W4 = W >> 2;
-    const float* __restrict__ inb = a.in + (size_t)bq * a.cin * (DENSE ? H * W : H2 * (P4 ? W4 : W2));
-    const uint8_t* __restrict__ amb = DENSE ? nullptr : a.in_amax + (size_t)bs * a.cin * H2 * (P4 ? W4 : W2);
-    if constexpr (P4) {
-      // host contract: W / 4 % 4 == 0, so every 4-cell group is one aligned float4 / uint32
-      const int qy0 = (ty0 >> 1) - 1, cx0 = tx0 >> 2;
-#pragma unroll
-      for (int it = 0; it < SI4; ++it) {
-        const int i = tid + it * NT_;
-        const int row = i / Q16, q = i % Q16;
-        const int ci = row / CY, ry = row % CY;
-        const int cy = qy0 + ry, cx = cx0 + 4 * q, c = c0 + ci;
-        const bool ok = i < SROWS * Q16 && cy >= 0 && cy < H2 && c < a.cin && cx < W4;
-        const int o = ok ? (c * H2 + cy) * W4 + cx : 0;
-        const float4 v = *reinterpret_cast<const float4*>(inb + o);
-        const uint32_t am = *reinterpret_cast<const uint32_t*>(amb + o);
-        st_i[it] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        st_ia[it] = ok ? am : 0xffffffffu;   // 0xff names no pixel of a 2 x 4 window
-      }
-#pragma unroll
-      for (int it = 0; it < SH; ++it) {
-        const int i = tid + it * NT_;
-        const int row = i >> 1, side = i & 1;
-        const int ci = row / CY, ry = row % CY;
-        const int cy = qy0 + ry, cx = side ? cx0 + TW / 4 : cx0 - 1, c = c0 + ci;
-        const bool ok = i < SROWS * 2 && cy >= 0 && cy < H2 && cx >= 0 && cx < W4 && c < a.cin;
-        const int o = ok ? (c * H2 + cy) * W4 + cx : 0;
-        const float v = inb[o];
-        const int am = (int)amb[o];
-        st_h[it] = ok ? v : 0.f;
-        st_ha[it] = ok ? am : 0xff;
-      }
-    } else if constexpr (DENSE) {
-      if ((W & 3) == 0) {
-#pragma unroll
-        for (int it = 0; it < DI; ++it) {
-          const int i = tid + it * NT_;
-          const int row = i / Q4, q = i % Q4;
-          const int ci = row / HY, hy = row % HY;
-          const int gy = ty0 - 1 + hy, gx = tx0 + 4 * q, c = c0 + ci;
-          const bool ok = i < DROWS * Q4 && gy >= 0 && gy < H && c < a.cin && gx < W;
-          const int o = ok ? (c * H + gy) * W + gx : 0;
-          const float4 v = *reinterpret_cast<const float4*>(inb + o);
-          st_i[it] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-      } else {
-#pragma unroll
-        for (int it = 0; it < DI; ++it) {
-          const int i = tid + it * NT_;
-          const int row = i / Q4, q = i % Q4;
-          const int ci = row / HY, hy = row % HY;
-          const int gy = ty0 - 1 + hy, gx = tx0 + 4 * q, c = c0 + ci;
-          const bool rok = i < DROWS * Q4 && gy >= 0 && gy < H && c < a.cin;
-          float vv[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const bool ok = rok && gx + e < W;
-            const int o = ok ? (c * H + gy) * W + gx + e : 0;
-            const float v = inb[o];
-            vv[e] = ok ? v : 0.f;
-          }
-          st_i[it] = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        }
-      }
-#pragma unroll
-      for (int it = 0; it < DH; ++it) {
-        const int i = tid + it * NT_;
-        const int row = i >> 1, side = i & 1;
-        const int ci = row / HY, hy = row % HY;
-        const int gy = ty0 - 1 + hy, gx = side ? tx0 + TW : tx0 - 1, c = c0 + ci;
-        const bool ok = i < DROWS * 2 && gy >= 0 && gy < H && gx >= 0 && gx < W && c < a.cin;
-        const int o = ok ? (c * H + gy) * W + gx : 0;
-        const float v = inb[o];
-        st_h[it] = ok ? v : 0.f;
-      }
-    } else {
-      const int qy0 = (ty0 >> 1) - 1, qx0 = (tx0 >> 1) - 1;
-      if ((W2 & 3) == 0) {
-#pragma unroll
-        for (int it = 0; it < SI; ++it) {
-          const int i = tid + it * NT_;
-          const int row = i / Q8, q = i % Q8;
-          const int ci = row / CY, ry = row % CY;
-          const int cy = qy0 + ry, cx = qx0 + 1 + 4 * q, c = c0 + ci;
-          const bool ok = i < SROWS * Q8 && 4 * q < TW / 2 && cy >= 0 && cy < H2 && c < a.cin && cx < W2;
-          const int o = ok ? (c * H2 + cy) * W2 + cx : 0;
-          const float4 v = *reinterpret_cast<const float4*>(inb + o);
-          const uint32_t am = *reinterpret_cast<const uint32_t*>(amb + o);
-          st_i[it] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-          st_ia[it] = ok ? am : 0x04040404u;
-        }
-      } else {
-#pragma unroll
-        for (int it = 0; it < SI; ++it) {
-          const int i = tid + it * NT_;
-          const int row = i / Q8, q = i % Q8;
-          const int ci = row / CY, ry = row % CY;
-          const int cy = qy0 + ry, cx = qx0 + 1 + 4 * q, c = c0 + ci;
-          const bool rok = i < SROWS * Q8 && 4 * q < TW / 2 && cy >= 0 && cy < H2 && c < a.cin;
-          float vv[4];
-          uint32_t aa = 0;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const bool ok = rok && cx + e < W2 && 4 * q + e < TW / 2;
-            const int o = ok ? (c * H2 + cy) * W2 + cx + e : 0;
-            const float v = inb[o];
-            const uint32_t am = amb[o];
-            vv[e] = ok ? v : 0.f;
-            aa |= (ok ? am : 4u) << (8 * e);
-          }
-          st_i[it] = make_float4(vv[0], vv[1], vv[2], vv[3]);
-          st_ia[it] = aa;
-        }
-      }
-#pragma unroll
-      for (int it = 0; it < SH; ++it) {
-        const int i = tid + it * NT_;
-        const int row = i >> 1, side = i & 1;
-        const int ci = row / CY, ry = row % CY;
-        const int cy = qy0 + ry, cx = side ? qx0 + CX - 1 : qx0, c = c0 + ci;
-        const bool ok = i < SROWS * 2 && cy >= 0 && cy < H2 && cx >= 0 && cx < W2 && c < a.cin;
-        const int o = ok ? (c * H2 + cy) * W2 + cx : 0;
-        const float v = inb[o];
-        const int am = (int)amb[o];
-        st_h[it] = ok ? v : 0.f;
-        st_ha[it] = ok ? am : 4;
-      }
-    }
-    // weights: rows [c0*9, c0*9 + KC) of every set, contiguous (k = ci*9 + tap)
-#pragma unroll
-    for (int it = 0; it < WIT; ++it) {
-      const int idx = tid + it * NT_;
-      const int g = idx / (KCP * (COUT / 4)), rem = idx % (KCP * (COUT / 4));
-      const int k = rem / (COUT / 4), c4 = (rem % (COUT / 4)) * 4;
-      const bool ok = idx < NWV && k < KC;
-      const float4 v = *reinterpret_cast<const float4*>(a.wts + (ok ? ((size_t)g * 9 * CIN + c0 * 9 + k) * COUT + c4 : 0));
-      st_w[it] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-
-  // one pool cell -> its 2x2 pixels at halo rows 2ry-1, 2ry and LDS columns 2rx-1+XO, 2rx+XO
-  __device__ __forceinline__ static void put_cell(float* halo, int ci, int ry, int rx, float v, int sb) {
-    float* d = halo + ci * PLANE + (2 * ry - 1) * RS + 2 * rx - 1 + XO;
-    if (ry > 0) *reinterpret_cast<float2*>(d) = make_float2(sb == 0 ? v : 0.f, sb == 1 ? v : 0.f);
-    if (ry < CY - 1) *reinterpret_cast<float2*>(d + RS) = make_float2(sb == 2 ? v : 0.f, sb == 3 ? v : 0.f);
-  }
-
-  // one 2 x 4 cell -> its 8 pixels: halo rows 2ry-1, 2ry, LDS columns 4rx .. 4rx+3 (halo columns
-  // 4rx-3 .. 4rx; rx = 0 and TW/4 + 1 are the halo cells, whose other columns are row padding)
-  __device__ __forceinline__ static void put_cell4(float* halo, int ci, int ry, int rx, float v, int sb) {
-    float* d = halo + ci * PLANE + (2 * ry - 1) * RS + 4 * rx;
-    if (ry > 0)
-      *reinterpret_cast<float4*>(d) = make_float4(sb == 0 ? v : 0.f, sb == 1 ? v : 0.f, sb == 2 ? v : 0.f, sb == 3 ? v : 0.f);
-    if (ry < CY - 1)
-      *reinterpret_cast<float4*>(d + RS) =
-          make_float4(sb == 4 ? v : 0.f, sb == 5 ? v : 0.f, sb == 6 ? v : 0.f, sb == 7 ? v : 0.f);
-  }
-
-  __device__ __forceinline__ void store(float* halo, float* wl, int tid) const {
-    if constexpr (P4) {
-      static_assert(XO == 3, "P4 cells land on 16-byte aligned columns 4 rx");
-#pragma unroll
-      for (int it = 0; it < SI4; ++it) {
-        const int i = tid + it * NT_;
-        if (i < SROWS * Q16) {
-          const int row = i / Q16, q = i % Q16;
-          const int ci = row / CY, ry = row % CY;
-          const float vv[4] = {st_i[it].x, st_i[it].y, st_i[it].z, st_i[it].w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            put_cell4(halo, ci, ry, 1 + 4 * q + e, vv[e], (int)((st_ia[it] >> (8 * e)) & 0xffu));
-        }
-      }
-#pragma unroll
-      for (int it = 0; it < SH; ++it) {
-        const int i = tid + it * NT_;
-        if (i < SROWS * 2) {
-          const int row = i >> 1, side = i & 1;
-          put_cell4(halo, row / CY, row % CY, side ? TW / 4 + 1 : 0, st_h[it], st_ha[it]);
-        }
-      }
-    } else if constexpr (DENSE) {
-#pragma unroll
-      for (int it = 0; it < DI; ++it) {
-        const int i = tid + it * NT_;
-        if (i < DROWS * Q4) {
-          const int row = i / Q4, q = i % Q4;
-          const int ci = row / HY, hy = row % HY;
-          *reinterpret_cast<float4*>(halo + ci * PLANE + hy * RS + 1 + XO + 4 * q) = st_i[it];
-        }
-      }
-#pragma unroll
-      for (int it = 0; it < DH; ++it) {
-        const int i = tid + it * NT_;
-        if (i < DROWS * 2) {
-          const int row = i >> 1, side = i & 1;
-          const int ci = row / HY, hy = row % HY;
-          halo[ci * PLANE + hy * RS + (side ? HX - 1 : 0) + XO] = st_h[it];
-        }
-      }
-    } else {
-#pragma unroll
-      for (int it = 0; it < SI; ++it) {
-        const int i = tid + it * NT_;
-        const int q = i % Q8;
-        if (i < SROWS * Q8 && 4 * q < TW / 2) {
-          const int row = i / Q8;
-          const int ci = row / CY, ry = row % CY;
-          const float vv[4] = {st_i[it].x, st_i[it].y, st_i[it].z, st_i[it].w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (4 * q + e < TW / 2) put_cell(halo, ci, ry, 1 + 4 * q + e, vv[e], (int)((st_ia[it] >> (8 * e)) & 0xffu));
-        }
-      }
-#pragma unroll
-      for (int it = 0; it < SH; ++it) {
-        const int i = tid + it * NT_;
-        if (i < SROWS * 2) {
-          const int row = i >> 1, side = i & 1;
-          put_cell(halo, row / CY, row % CY, side ? CX - 1 : 0, st_h[it], st_ha[it]);
-        }
-      }
-    }
-#pragma unroll
-    for (int it = 0; it < WIT; ++it) {
-      const int idx = tid + it * NT_;
-      if (idx < NWV) *reinterpret_cast<float4*>(wl + (size_t)idx * 4) = st_w[it];
-    }
-  }
-};
-
-// ---- MFMA over one staged chunk.  k = k0 + h (h = lane half) with k = ci*9 + tap: the halo
-//      offset pattern repeats every 9 k-steps (two channels), so every LDS read in the fully
-//      unrolled loop is a per-lane base register + immediate.  Operands of step k0 are read
-//      one step ahead (explicit software pipeline). ----
-template <class Cfg, int PD = 1>
-__device__ __forceinline__ void mfma_chunk(const float* halo, const float* wl, const int (&pix_off)[Cfg::MPW],
-                                           int lane, int wn, f32x16 (&acc)[Cfg::NG_][Cfg::MPW][Cfg::NPW]) {
-  constexpr int MPW = Cfg::MPW, NPW = Cfg::NPW, NG = Cfg::NG_, COUT = Cfg::COUT_;
-  constexpr int KC = Cfg::KC, KCP = Cfg::KCP, PLANE = Cfg::PLANE, RS = Cfg::RS, EPI = Cfg::EPI_;
-  const int h = lane >> 5;
-  // Halo offset of k = k0 + h (k = ci * 9 + tap):  off(k0) + h * delta(k0 % 9), with off(k0) a
-  // compile-time immediate (the loop is unrolled) and delta one of three values: +1 inside a tap
-  // row, RS - 2 from the row's last tap to the next row, PLANE - 2 RS - 2 from tap 8 to the next
-  // channel's tap 0.  So each m-tile needs three per-lane base registers (pix_off + h * delta)
-  // instead of one per k-step pattern, and every operand read is base + immediate.
-  constexpr int DLT[3] = {1, RS - 2, PLANE - 2 * RS - 2};
-  int xb[MPW][3];
-#pragma unroll
-  for (int u = 0; u < MPW; ++u)
-#pragma unroll
-    for (int t = 0; t < 3; ++t) xb[u][t] = pix_off[u] + h * DLT[t];
-  auto read_x = [&](int k0, float (&xv)[MPW]) {
-    const int r9 = k0 % 9;
-    const int off = (k0 / 9) * PLANE + (r9 / 3) * RS + (r9 % 3);
-    const int t = (r9 == 8) ? 2 : (r9 == 2 || r9 == 5) ? 1 : 0;
-#pragma unroll
-    for (int u = 0; u < MPW; ++u) {
-      if constexpr (KC % 2 == 0) xv[u] = halo[xb[u][t] + off];
-      else xv[u] = (k0 + h < KC) ? halo[xb[u][t] + off] : 0.f;
-    }
-  };
-  auto read_w = [&](int k0, float (&wv)[NG][NPW]) {
-#pragma unroll
-    for (int v = 0; v < NPW; ++v)
-#pragma unroll
-      for (int g = 0; g < NG; ++g) wv[g][v] = wl[((size_t)g * KCP + k0 + h) * COUT + (wn * NPW + v) * 32 + (lane & 31)];
-  };
-  // operand ring: step k0's operands are read PD steps ahead
-  float xr[PD + 1][MPW], wr[PD + 1][NG][NPW];
-#pragma unroll
-  for (int d = 0; d < PD; ++d)
-    if (2 * d < KCP) {
-      read_x(2 * d, xr[d]);
-      read_w(2 * d, wr[d]);
-    }
-#pragma unroll
-  for (int k0 = 0; k0 < KCP; k0 += 2) {
-    const int cur = (k0 / 2) % (PD + 1), nxt = (k0 / 2 + PD) % (PD + 1);
-    if (k0 + 2 * PD < KCP) {
-      read_x(k0 + 2 * PD, xr[nxt]);
-      read_w(k0 + 2 * PD, wr[nxt]);
-    }
-    if constexpr (Cfg::PIN) __builtin_amdgcn_sched_barrier(0);   // keep the ring (see DRSA_CONV_PIN_SMALL)
-#pragma unroll
-    for (int v = 0; v < NPW; ++v)
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int u = 0; u < MPW; ++u) {
-          float x = xr[cur][u];
-          // NG == 2 is the Gamma forward on a non-negative input (ABI contract): x+ = x, so both
-          // sets read the same operand with no per-k-step transform
-          if constexpr (EPI < EPI_BWD && NG == 3) {
-            x = (g == 0) ? x : (g == 1 ? fmaxf(x, 0.f) : fminf(x, 0.f));
-          }
-          acc[g][u][v] = mfma32(wr[cur][g][v], x, acc[g][u][v]);
-        }
-  }
-}
-// ---- bf16 staging (ET = 1) of one 16-channel chunk.  Item (half, hy, hx) = the 8 channels
-//      c0 + 8 half .. +7 of halo pixel (hy, hx): 8 coalesced fp32 loads (consecutive lanes on
-//      consecutive pixels), rounded and packed at store time into one 16-byte LDS slot.  Weights
-//      come pre-laid-out and pre-rounded ([NG][CIN/16][9][2][COUT][8] bf16): a straight copy. ----
-template <class Cfg, int NT_ = kThreads>
-struct StagerBF {
-  static constexpr int CIN = Cfg::CIN_, COUT = Cfg::COUT_, NG = Cfg::NG_, HY = Cfg::HY, HX = Cfg::HX;
-  static constexpr int HXB = Cfg::HXB, NCH = CIN / 16;
-  static constexpr int NITEM = 2 * HY * HX, IT = (NITEM + NT_ - 1) / NT_;
-  static constexpr int NWQ = NG * 18 * COUT, WIT = (NWQ + NT_ - 1) / NT_;
-  // (2,4) pool-sparse staging: one item per (channel half, halo row, pool cell): the cell's 8
-  // channel values and argmax bytes are loaded once and expanded to its 4 pixels at store time
-  // (the generic per-pixel item would load each cell 4 times)
-  static constexpr bool P4 = Cfg::AMODE_ == A_POOLSPARSE && Cfg::PW_ == 4;
-  static constexpr int NCR = Cfg::TW_ / 4 + 2;                 // cells per halo row (2 partial)
-  static constexpr int NITEM4 = 2 * HY * NCR, IT4 = (NITEM4 + NT_ - 1) / NT_;
-  static constexpr int ITX = P4 ? IT4 : IT;
-  float st_f[ITX][8];
-  uint32_t st_a[P4 ? IT4 : 1][2];
-  uint4 st_w[WIT];
-
-  __device__ __forceinline__ void load(const ConvArgs& a, int c0, int tid, int ty0, int tx0, int bq, int bs) {
-    const int H = a.H, W = a.W;
-    const unsigned HW = (unsigned)(H * W);
-    // per-sample bases (uniform) + 32-bit per-lane offsets (saddr + voffset loads)
-    const int H2s = H >> 1, W2s = W / (P4 ? 4 : Cfg::PW_);
-    const float* __restrict__ inb =
-        a.in + (size_t)bq * a.cin * (Cfg::AMODE_ == A_POOLSPARSE || P4 ? (size_t)H2s * W2s : (size_t)HW);
-    const uint8_t* __restrict__ amb = (Cfg::AMODE_ == A_POOLSPARSE || P4) ? a.in_amax + (size_t)bs * a.cin * H2s * W2s
-                                                                          : nullptr;
-    if constexpr (P4) {
-      const int H2 = H >> 1, W2 = W >> 2;
-      const unsigned HW2 = (unsigned)(H2 * W2);
-#pragma unroll
-      for (int it = 0; it < IT4; ++it) {
-        const int i = tid + it * NT_;
-        const int cs = i % NCR, r = i / NCR, hy = r % HY, half = r / HY;
-        const int gy = ty0 - 1 + hy, cx = (tx0 >> 2) - 1 + cs, cb = c0 + 8 * half;
-        const bool ok = i < NITEM4 && gy >= 0 && gy < H && cx >= 0 && cx < W2;
-        const unsigned cell = ok ? (unsigned)((gy >> 1) * W2 + cx) : 0u;
-        const unsigned base = ok ? (unsigned)cb * HW2 + cell : 0u;
-        uint32_t ab[2] = {0u, 0u};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const bool okc = ok && cb + j < a.cin;
-          const float v = inb[okc ? base + j * HW2 : 0u];
-          const uint32_t am = amb[okc ? base + j * HW2 : 0u];
-          st_f[it][j] = okc ? v : 0.f;
-          ab[j >> 2] |= (okc ? am : 0xffu) << (8 * (j & 3));   // 0xff matches no pixel
-        }
-        st_a[it][0] = ab[0];
-        st_a[it][1] = ab[1];
-      }
-    } else if constexpr (Cfg::AMODE_ == A_POOLSPARSE) {
-      // backward input at 2 x PW pool resolution + argmax byte (the pool backward; PW = 4: the
-      // VGGish (2,4) pool, create_model.py:61): halo pixel (gy, gx) holds g[cell] where the cell's
-      // argmax (row-major window position) is this pixel, else 0
-      constexpr int PWB = Cfg::PW_;
-      const int H2 = H >> 1, W2 = W / PWB;
-      const unsigned HW2 = (unsigned)(H2 * W2);
-#pragma unroll
-      for (int it = 0; it < IT; ++it) {
-        const int i = tid + it * NT_;
-        const int hx = i % HX, r = i / HX, hy = r % HY, half = r / HY;
-        const int gy = ty0 - 1 + hy, gx = tx0 - 1 + hx, cb = c0 + 8 * half;
-        const bool ok = i < NITEM && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        const unsigned cell = ok ? (unsigned)((gy >> 1) * W2 + (gx / PWB)) : 0u;
-        const unsigned base = ok ? (unsigned)cb * HW2 + cell : 0u;
-        const uint32_t sub = (uint32_t)((gy & 1) * PWB + (gx % PWB));
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const bool okc = ok && cb + j < a.cin;
-          const float v = inb[okc ? base + j * HW2 : 0u];
-          const uint32_t am = amb[okc ? base + j * HW2 : 0u];
-          st_f[it][j] = (okc && am == sub) ? v : 0.f;
-        }
-      }
-    } else {
-#pragma unroll
-      for (int it = 0; it < IT; ++it) {
-        const int i = tid + it * NT_;
-        const int hx = i % HX, r = i / HX, hy = r % HY, half = r / HY;
-        const int gy = ty0 - 1 + hy, gx = tx0 - 1 + hx, cb = c0 + 8 * half;
-        const bool ok = i < NITEM && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        const unsigned base = ok ? (unsigned)cb * HW + (unsigned)(gy * W + gx) : 0u;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const bool okc = ok && cb + j < a.cin;
-          const float v = inb[okc ? base + j * HW : 0u];
-          st_f[it][j] = okc ? v : 0.f;
-        }
-      }
-    }
-    const uint4* wq = reinterpret_cast<const uint4*>(a.wts);
-    const int chunk = c0 / 16;
-#pragma unroll
-    for (int it = 0; it < WIT; ++it) {
-      const int idx = tid + it * NT_;
-      const bool ok = idx < NWQ;
-      const int g = idx / (18 * COUT), rem = idx % (18 * COUT);
-      st_w[it] = wq[ok ? ((size_t)g * NCH + chunk) * 18 * COUT + rem : 0];
-    }
-  }
-
-  __device__ __forceinline__ void store(float* halo, float* wl, int tid, int ty0 = 0, int tx0 = 0) const {
-    uint4* hb = reinterpret_cast<uint4*>(halo);
-    if constexpr (P4) {
-#pragma unroll
-      for (int it = 0; it < IT4; ++it) {
-        const int i = tid + it * NT_;
-        if (i < NITEM4) {
-          const int cs = i % NCR, r = i / NCR, hy = r % HY;
-          const uint32_t rowsub = (uint32_t)(((ty0 - 1 + hy) & 1) * 4);
-          // cell cs covers halo columns 4 cs - 3 .. 4 cs (halo column hx = pixel tx0 - 1 + hx)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int hx = 4 * cs - 3 + e;
-            if (hx >= 0 && hx < HX) {
-              float v8[8];
-#pragma unroll
-              for (int j = 0; j < 8; ++j) {
-                const uint32_t am = (st_a[it][j >> 2] >> (8 * (j & 3))) & 0xffu;
-                v8[j] = am == rowsub + (uint32_t)e ? st_f[it][j] : 0.f;
-              }
-              uint4 q;
-              q.x = pack_bf16x2(v8[0], v8[1]);
-              q.y = pack_bf16x2(v8[2], v8[3]);
-              q.z = pack_bf16x2(v8[4], v8[5]);
-              q.w = pack_bf16x2(v8[6], v8[7]);
-              hb[r * HXB + hx] = q;
-            }
-          }
-        }
-      }
-    } else {
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int i = tid + it * NT_;
-      if (i < NITEM) {
-        const int hx = i % HX, r = i / HX;
-        uint4 q;
-        q.x = pack_bf16x2(st_f[it][0], st_f[it][1]);
-        q.y = pack_bf16x2(st_f[it][2], st_f[it][3]);
-        q.z = pack_bf16x2(st_f[it][4], st_f[it][5]);
-        q.w = pack_bf16x2(st_f[it][6], st_f[it][7]);
-        hb[r * HXB + hx] = q;   // r = half * HY + hy
-      }
-    }
-    }
-    uint4* wb = reinterpret_cast<uint4*>(wl);
-#pragma unroll
-    for (int it = 0; it < WIT; ++it) {
-      const int idx = tid + it * NT_;
-      if (idx < NWQ) wb[idx] = st_w[it];
-    }
-  }
-};
-
-// x+ / x- of 8 packed bf16 (sign bit per 16-bit half): Gamma's NG = 3 forward on a signed input
-__device__ __forceinline__ uint32_t bf2_neg_mask(uint32_t w) { return ((w >> 15) & 0x00010001u) * 0xffffu; }
-
-// ---- bf16 MFMA over one staged 16-channel chunk: one v_mfma_f32_32x32x16_bf16 per tap and
-//      (set, m-tile, n-tile); lane l reads its 8 channels (half l>>5) of pixel l&31 (B) and of
-//      output channel l&31 (A) as one ds_read_b128 each, one tap ahead. ----
-template <class Cfg>
-__device__ __forceinline__ void mfma_chunk_bf(const uint4* hb, const uint4* wb, const int (&pix_off)[Cfg::MPW],
-                                              int lane, int wn, f32x16 (&acc)[Cfg::NG_][Cfg::MPW][Cfg::NPW]) {
-  constexpr int MPW = Cfg::MPW, NPW = Cfg::NPW, NG = Cfg::NG_, COUT = Cfg::COUT_, HXB = Cfg::HXB;
-  const uint4* wlane = wb + (lane >> 5) * COUT + wn * NPW * 32 + (lane & 31);
-  uint4 xr[2][MPW], wr[2][NG][NPW];
-  auto rd = [&](int t, uint4 (&x)[MPW], uint4 (&w)[NG][NPW]) {
-    const int toff = (t / 3) * HXB + t % 3;
-#pragma unroll
-    for (int u = 0; u < MPW; ++u) x[u] = hb[pix_off[u] + toff];
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-      for (int v = 0; v < NPW; ++v) w[g][v] = wlane[(g * 9 + t) * 2 * COUT + v * 32];
-  };
-  rd(0, xr[0], wr[0]);
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    const int cur = t & 1;
-    if (t + 1 < 9) rd(t + 1, xr[cur ^ 1], wr[cur ^ 1]);
-#pragma unroll
-    for (int v = 0; v < NPW; ++v)
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int u = 0; u < MPW; ++u) {
-          uint4 b = xr[cur][u];
-          if constexpr (NG == 3) {
-            if (g > 0) {
-              const uint4 m = make_uint4(bf2_neg_mask(b.x), bf2_neg_mask(b.y), bf2_neg_mask(b.z), bf2_neg_mask(b.w));
-              b = (g == 1) ? make_uint4(b.x & ~m.x, b.y & ~m.y, b.z & ~m.z, b.w & ~m.w)
-                           : make_uint4(b.x & m.x, b.y & m.y, b.z & m.z, b.w & m.w);
-            }
-          }
-          acc[g][u][v] = mfma32_bf16(__builtin_bit_cast(u16x8, wr[cur][g][v]), __builtin_bit_cast(u16x8, b),
-                                     acc[g][u][v]);
-        }
-  }
-}
 
 // PW: pool window width of EPI_FWD_POOL (2 x PW windows; 4 = VGGish's (2,4) pool)
 template <int CIN, int COUT, int TH, int TW, int MW, int CIC, int NG, int AMODE, int EPI, int ET = 0, int PW = 2>
@@ -1225,77 +557,5 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(ConvCf
 #endif
 #undef CONV_STAMP
 }
-
-typedef void (*KernFn)(ConvArgs);
-
-struct Entry {
-  int cin_p, cout_p, th, tw, mw, cic, ng, amode, epi;
-  KernFn fn;
-  size_t lds;
-  int et = 0;   // operand type (ConvCfg ET)
-  int pw = 2;   // pool window width (ConvCfg PW)
-};
-
-struct Table {
-  const Entry* entries;
-  int n;
-};
-
-// One table entry from the eleven template arguments of ConvCfg / conv3x3_kernel, in their order:
-// CIN, COUT, TH, TW, MW, CIC, NG, AMODE, EPI, ET, PW
-template <int... P>
-constexpr Entry conv_entry() {
-  static_assert(sizeof...(P) == 11, "CONV_ENTRY takes every ConvCfg parameter");
-  constexpr int p[] = {P...};
-  return Entry{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8],
-               conv3x3_kernel<P...>, ConvCfg<P...>::lds_floats * sizeof(float), p[9], p[10]};
-}
-#define CONV_ENTRY(CIN, COUT, TH, TW, MW, CIC, NG, AM, EP, ET, PW) \
-  drsa_conv::conv_entry<CIN, COUT, TH, TW, MW, CIC, NG, AM, EP, ET, PW>()
-
-// tile family (the choice: lrp_conv.hip find): 8x32 / 8x16 (MW 8), 8x8 (MW 4)
-#define CONV_FAMILY(CIN, COUT, CIC, NG, AM, EP, ET, PW)       \
-  CONV_ENTRY(CIN, COUT, 8, 32, 8, CIC, NG, AM, EP, ET, PW),   \
-  CONV_ENTRY(CIN, COUT, 8, 16, 8, CIC, NG, AM, EP, ET, PW),   \
-  CONV_ENTRY(CIN, COUT, 8, 8, 4, CIC, NG, AM, EP, ET, PW)
-
-// forward: every denominator set count and both epilogues (2x2 pool, ReLU only)
-#define FWD_SET_ET(CIN, COUT, CIC, ET)                                                      \
-  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 2),        \
-  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 2),        \
-  CONV_FAMILY(CIN, COUT, CIC, 3, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 2),        \
-  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_RELU, ET, 2),        \
-  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_RELU, ET, 2),        \
-  CONV_FAMILY(CIN, COUT, CIC, 3, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_RELU, ET, 2)
-#define FWD_SET(CIN, COUT, CIC) FWD_SET_ET(CIN, COUT, CIC, 0)
-// bf16-operand forward (ET = 1, 16-channel chunks)
-#define FWD_SET_BF(CIN, COUT) FWD_SET_ET(CIN, COUT, 16, 1)
-
-// 2x4-pool forward (VGGish block 1, create_model.py:61): fp32 and bf16 operands
-#define FWD_SET_P4(CIN, COUT, CIC, ET)                                                      \
-  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 4),        \
-  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 4),        \
-  CONV_FAMILY(CIN, COUT, CIC, 3, drsa_conv::A_DENSE, drsa_conv::EPI_FWD_POOL, ET, 4)
-
-// fp32 per-clone backward: one or two weight sets, dense and 2x2-pool-sparse g
-#define BWD_SET(CIN, COUT, CIC)                                                             \
-  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_DENSE, drsa_conv::EPI_BWD, 0, 2),              \
-  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_DENSE, drsa_conv::EPI_BWD, 0, 2),              \
-  CONV_FAMILY(CIN, COUT, CIC, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 0, 2),         \
-  CONV_FAMILY(CIN, COUT, CIC, 2, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 0, 2)
-
-// bf16-operand per-clone backward (ET = 1), dense and pool-sparse g, one weight set
-#define BWD_SET_BF(CIN, COUT)                                                               \
-  CONV_FAMILY(CIN, COUT, 16, 1, drsa_conv::A_DENSE, drsa_conv::EPI_BWD, 1, 2),               \
-  CONV_FAMILY(CIN, COUT, 16, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 1, 2)
-// bf16-operand per-clone backward with g at (2,4)-pool resolution (VGGish block 1)
-#define BWD_SET_BF_P4(CIN, COUT) CONV_FAMILY(CIN, COUT, 16, 1, drsa_conv::A_POOLSPARSE, drsa_conv::EPI_BWD, 1, 4)
-
-// A conv_*.hip file's entries and its table (listed in lrp_conv.hip's DRSA_CONV_TABLES)
-#define CONV_TABLE(NAME, ...)                                                                     \
-  namespace drsa_conv {                                                                           \
-  static const Entry NAME##_e[] = {__VA_ARGS__};                                                  \
-  extern const Table NAME = {NAME##_e, (int)(sizeof(NAME##_e) / sizeof(NAME##_e[0]))};            \
-  }
 
 }  // namespace drsa_conv

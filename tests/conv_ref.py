@@ -209,7 +209,8 @@ FWD_COMBOS = [(1, "computed"), (2, "computed"), (3, "computed"), (1, "map"), (1,
 
 
 def tile_width(fwd, cin, cout, W, bf16=False):
-    """Tile width lrp_conv.hip's find() picks (8 x 32, 8 x 16 or 8 x 8 tiles); cin -> cout are the
+    """Tile width of the tile rule (csrc/lrp_conv_config.h wide_tile_w(): 8 x 32, 8 x 16 or 8 x 8 tiles at
+    W >= 32, 8 x 8 below; the tables hold exactly those two per kernel set); cin -> cout are the
     call's own channel counts (a backward call: g channels -> output channels).  An 8-wide entry
     runs as 4 x 8 tiles while its grid has fewer than SMALL_WG workgroups (fp32 only)."""
     ci, co = pad32(cin), pad32(cout)

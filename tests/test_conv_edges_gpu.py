@@ -1,4 +1,5 @@
-"""The 3x3 conv kernels (csrc/lrp_conv_kernel.h, conv_small.hip, conv_first.hip) at partial tiles and
+"""The 3x3 conv kernels (csrc/lrp_conv_kernel.h and its parts, the conv_*.hip tables, conv_small.hip,
+conv_first.hip) at partial tiles and
 padded channel counts, through the C ABI, against the CPU reference tests/conv_ref.py (GPU).
 
 fp32: every output is bit-identical to the reference (oracle/lrp_exact.c's k-ordered fma chains plus
@@ -13,7 +14,7 @@ element of the view still holds the prefill.  An output that is not requested is
 Every case first asserts its ``*_has_kernel*`` query; none is skipped.
 
 Shapes (H, W), the smallest that reach each path:
-  (12, 40)  H = 8 + 4; W = 32 + 8 / 16 + 16 + 8 / 5 x 8 by tile family; W/2 = 20 aligned sparse staging
+  (12, 40)  H = 8 + 4; W = 32 + 8 / 16 + 16 + 8 / 5 x 8 by the pair's wide tile; W/2 = 20 aligned sparse staging
   (6, 12)   one partial tile per row on 8 x 8 and 4 x 8 tiles; W/2 = 6 per-cell sparse staging
   (10, 20)  W/2 = 10 per-cell sparse staging
   (6, 36)   W >= 32 with W/2 = 18 per-cell sparse staging and W % 8 != 0
@@ -28,9 +29,9 @@ samples are replicated, the reference is computed for the two, every replica is 
 
 Dropped from the cross product (tests/conv_ref.py builds the lists): per (pair, shape, pool) the
 forward runs two of the seven (ng, den) combinations {1, 2, 3} x {none, computed} + (1, map),
-rotating, so every pair runs on every tile family it reaches and every combination runs on every
-family; per (pair, shape, dense / sparse g) the backward runs two of the four modes, rotating so
-that every pair sees all eight (g, mode) combinations on each of its tile families; the 2x4 pool and the
+rotating, so every pair runs on both of its tiles (the wide one and 8 x 8) and every combination runs on every
+tile shape; per (pair, shape, dense / sparse g) the backward runs two of the four modes, rotating so
+that every pair sees all eight (g, mode) combinations on each of its tiles; the 2x4 pool and the
 den_map / den_ring entry points run on the pairs listed there, not on all eight; bf16 runs three
 pairs (+ 64->64 for the 2x4 pool) on four shapes with ng rotating.
 """

@@ -5,7 +5,7 @@ have fewer than 512 workgroups, so which kernel a layer runs depends on the batc
 output one k-ordered fp32 chain (k = ci * 9 + tap), so a sample's outputs must not depend on the
 batch it is run in: each case runs the same leading samples once in a batch below the threshold
 (4 x 8 tiles) and once in a batch at the threshold (8 x 8 tiles) and asserts bit equality, for every
-replaced family: forwards with 2 x 2 pool or ReLU only, NG 1-3 (with the denominator output), and
+replaced kernel set: forwards with 2 x 2 pool or ReLU only, NG 1-3 (with the denominator output), and
 backwards with dense and pool-sparse g, NG 1 / 2, no post, POST_DIV and POST_MASK, 1 and 2 clones."""
 import pytest
 import torch
