@@ -71,9 +71,13 @@ _SKIP = object()
 
 def _frozen(v):
     """A rule field as a hashable key part: scalars as they are, lists / tuples / sets (zero_params
-    may be given as any of them) as tuples, anything else (tensors, callables) left out."""
+    may be given as any of them) as tuples, tensors (ZBox bounds) by shape, dtype and content -- not
+    by identity: an in-place edit recompiles, an equal copy does not --, anything else (callables) left out."""
     if v is None or isinstance(v, (bool, int, float, str)):
         return v
+    if isinstance(v, torch.Tensor):
+        t = v.detach().cpu().contiguous()
+        return ("tensor", tuple(t.shape), str(t.dtype), t.reshape(-1).view(torch.uint8).numpy().tobytes())
     if isinstance(v, (list, tuple, set, frozenset)):
         items = sorted(v, key=repr) if isinstance(v, (set, frozenset)) else v
         parts = tuple(_frozen(i) for i in items)

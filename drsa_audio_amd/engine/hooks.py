@@ -9,7 +9,7 @@ mapped module hooked the way zennit attaches its hooks (forward hook storing the
 backward hook replacing the input gradient):
 
 * a custom hook: its ``backward`` is called as is;
-* the built-in rule descriptors (Epsilon, Gamma, WSquare, Flat, ZPlus, AlphaBeta, Norm, Pass):
+* the built-in rule descriptors (Epsilon, Gamma, WSquare, Flat, ZPlus, AlphaBeta, ZBox, Norm, Pass):
   the modified-gradient arithmetic of zennit 0.5.1's BasicHook for that rule, on the stored
   input (SURVEY.md Appendix A; the same arithmetic the HIP plan fuses into its kernels);
 * unmapped modules: the plain gradient.
@@ -107,6 +107,17 @@ def rule_relevance(rule, m: nn.Module, x: torch.Tensor, R: torch.Tensor) -> torc
             with torch.enable_grad():
                 out = _aff(m, ins, w2, b2)
             return torch.autograd.grad(out, ins, g)[0]
+        if kind == "zbox":
+            # zennit ZBox: inputs (x, l, h) on the parameters (W, b), (W+, b+), (W-, b-); the output
+            # reducer (z - zl) - zh, the input reducer x grad_x - l grad_l - h grad_h
+            lo, hi = rule.bounds(x)
+            wp, wn = w.clamp(min=0), w.clamp(max=0)
+            bp, bn = mod(b, lambda t: t.clamp(min=0)), mod(b, lambda t: t.clamp(max=0))
+            den = (_aff(m, x, w, b) - _aff(m, lo, wp, bp)) - _aff(m, hi, wn, bn)
+            g = R / _stab(den, rule.stabilizer)
+            r = _grad([lambda t: _aff(m, t, w, b), lambda t: _aff(m, t, wp, bp), lambda t: _aff(m, t, wn, bn)],
+                      [x, lo, hi], [g, g, g])
+            return r[0] - r[1] - r[2]
         xp, xn = x.clamp(min=0), x.clamp(max=0)
         if kind == "gamma":
             gam = rule.gamma

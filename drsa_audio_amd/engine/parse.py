@@ -60,7 +60,7 @@ class ConvStage:
     W: torch.Tensor = None               # host, fp32 (bf16 plan: rounded to bf16 values)
     b: torch.Tensor = None
     rule: object = None
-    den_kind: Optional[str] = None       # "gamma" | "eps" | "map" | "ab" | None
+    den_kind: Optional[str] = None       # "gamma" | "eps" | "map" | "ab" | "box" | None
     ng_fwd: int = 1                      # weight groups of the forward / backward conv
     ng_bwd: int = 1
     bwd_bf16: bool = False               # the stage gets a bf16 backward weight set (schedule.mark_bwd_bf16)
@@ -81,6 +81,11 @@ class ConvStage:
     wts_bwd: torch.Tensor = None
     xmode_bwd: int = 0                   # XM_NONE
     w2_first: Optional[torch.Tensor] = None
+    # ZBox (first conv, one input channel): W+ / W- packed [2][cout][9] and b+ / b- [cout]; the bounds
+    # images and the rule's maps are per input shape, in den_maps
+    zb_wpn: Optional[torch.Tensor] = None
+    zb_bp: Optional[torch.Tensor] = None
+    zb_bn: Optional[torch.Tensor] = None
     den_maps: Dict[Tuple[int, int], torch.Tensor] = field(default_factory=dict)
     relu_name: Optional[str] = None      # features.<i> of the ReLU after the conv
     pool_name: Optional[str] = None      # features.<i> of the MaxPool2d (None: no pool)
@@ -120,7 +125,7 @@ class EngineError(NotImplementedError):
 DENSE_RULES = (None, "epsilon", "gamma", "zplus", "wsquare", "flat")
 # conv rule -> the form of its denominator (ConvStage.den_kind)
 _DEN_KIND = {None: None, "epsilon": "eps", "gamma": "gamma", "zplus": "gamma", "wsquare": "map", "flat": "map",
-             "alphabeta": "ab"}
+             "alphabeta": "ab", "zbox": "box"}
 
 
 @torch.no_grad()
@@ -250,8 +255,11 @@ def parse(model: nn.Module, composite, bf16: bool = False) -> Tuple[List[ConvSta
                 raise EngineError("engine: a ProjectionModel layer must be followed by MaxPool2d(2) or no pool")
         rule = rules.get(f"features.{name}")
         kind = _kind(rule)
-        if kind not in (None, "epsilon", "gamma", "wsquare", "flat", "zplus", "alphabeta"):
+        if kind not in (None, "epsilon", "gamma", "wsquare", "flat", "zplus", "alphabeta", "zbox"):
             raise EngineError(f"engine: rule {type(rule).__name__} on conv features.{name} is not supported yet")
+        if kind == "zbox" and (stages or m.in_channels != 1):
+            raise EngineError(f"engine: ZBox on features.{name} is not supported: it is the rule of the first "
+                              "conv of a one-channel input (the box bounds the network input)")
         if kind == "alphabeta" and (not prev_nonneg or (pool and pool_k != (2, 2))):
             raise EngineError(f"engine: AlphaBeta on features.{name} needs a non-negative input (not the first "
                               "conv) and a 2x2 or no max-pool after it")

@@ -174,6 +174,12 @@ class LRPEngine:
             st.W2, st.b2, bsets = rnd(W2.contiguous()), b2.contiguous(), [W2]
             if st.cin == 1:
                 st.w2_first = st.W2.reshape(st.cout, 9).contiguous()
+        elif k == "zbox":
+            # zennit ZBox: (x; W, b), (l; W+, b+), (h; W-, b-).  b = b+ + b- cancels in the denominator, so
+            # zero_params=("bias",) changes only roundings there and nothing in R_in: the plan is the same
+            Wr = rnd(W).reshape(st.cout, 9)
+            st.zb_wpn = torch.stack([Wr.clamp(min=0), Wr.clamp(max=0)]).contiguous()
+            st.zb_bp, st.zb_bn = b.clamp(min=0).contiguous(), b.clamp(max=0).contiguous()
         assert (len(sets), len(bsets)) == (st.ng_fwd, st.ng_bwd)
         st.wts_fwd, st.bias3, st.wts_bwd = fwd_layout(*sets), bias3, bwd_layout(*bsets)
         if self.bf16 and st.cin > 1:
@@ -210,6 +216,25 @@ class LRPEngine:
         if ("c4", H, W) not in st.den_maps:
             st.den_maps["c4", H, W] = self._den_map(st, H, W)[:, 1, 1].reshape(-1, 1).expand(-1, 4).contiguous()
         return st.den_maps["c4", H, W]
+
+    def _zbox_maps(self, st: ConvStage, H: int, W: int) -> Tuple[torch.Tensor, ...]:
+        """(low_img, high_img [H][W], zl, zh [cout][H][W]) of a ZBox first layer: the bounds spread over one
+        sample and the rule's two input-independent maps, made once per input shape like the WSquare map."""
+        if ("zbox", H, W) not in st.den_maps:
+            lo, hi = (t.reshape(H, W).contiguous() for t in
+                      st.rule.bounds(torch.empty(1, 1, H, W, device=self.device)))
+            zl, zh = (torch.empty(st.cout, H, W, device=self.device) for _ in range(2))
+            _capi.call("drsa_amd_first_layer_zbox_maps", st.zb_wpn[0].data_ptr(), st.zb_bp.data_ptr(),
+                       st.zb_wpn[1].data_ptr(), st.zb_bn.data_ptr(), lo.data_ptr(), hi.data_ptr(), zl.data_ptr(),
+                       zh.data_ptr(), st.cout, H, W, _capi.stream_ptr(self.device))
+            st.den_maps["zbox", H, W] = (lo, hi, zl, zh)
+        return st.den_maps["zbox", H, W]
+
+    def _zbox_den(self, st: ConvStage, a, amax, den, B, h, w, s):
+        """den = (a - zl) - zh at the argmax pixel (a pooled, with amax) or at every pixel (a at full resolution)."""
+        _, _, zl, zh = self._zbox_maps(st, h, w)
+        self._call(f"first_layer_zbox_den:{st.name}", "drsa_amd_first_layer_zbox_den", a.data_ptr(), _capi.ptr(amax),
+                   zl.data_ptr(), zh.data_ptr(), den.data_ptr(), B, st.cout, h, w, s)
 
     def _schedule(self, *key):
         """The (conv steps, dense steps) of (B, H, W, capture, stop_after, fanout), made once per key."""
@@ -278,9 +303,14 @@ class LRPEngine:
             tag, out = f"conv_fwd:{st.name}", y if sp.form == "fused" else a
             rec = {"in": cur, "H": h, "W": w, "Hout": ho, "Wout": wo, "a": a, "y": a if y is None else y, "amax": amax,
                    "den": den, "den_map": den_map}
+            # ZBox: the conv leaves no denominator; drsa_amd_first_layer_zbox_den forms it from the conv's output
+            box = st.den_kind == "box" and den is not None
             if sp.form == "unfused":
                 den_full = self._buf((li, "den_full"), (B, C, h, w)) if den is not None else None
-                self._conv_fwd(tag, sp.fwd, st, False, cur, den_map, a, None, den_full, B, h, w, st.ng_fwd, 0, s)
+                self._conv_fwd(tag, sp.fwd, st, False, cur, den_map, a, None, None if box else den_full, B, h, w,
+                               st.ng_fwd, 0, s)
+                if box:
+                    self._zbox_den(st, a, None, den_full, B, h, w, s)
                 self._call(f"maxpool:{st.pool_name}", "drsa_amd_maxpool_capture", a.data_ptr(), _capi.ptr(den_full),
                            y.data_ptr(), amax.data_ptr(), _capi.ptr(den), B, C, h, w, *st.pool_k, s)
             elif sp.den == "ring":
@@ -288,7 +318,10 @@ class LRPEngine:
                 self._call(tag, sp.fwd, cur.data_ptr(), st.wts_fwd.data_ptr(), st.bias3.data_ptr(), den_map.data_ptr(),
                            y.data_ptr(), amax.data_ptr(), den.data_ptr(), B, C, h, w, st.ng_fwd, s)
             else:
-                self._conv_fwd(tag, sp.fwd, st, False, cur, den_map, out, amax, den, B, h, w, st.ng_fwd, sp.pool, s)
+                self._conv_fwd(tag, sp.fwd, st, False, cur, den_map, out, amax, None if box else den, B, h, w,
+                               st.ng_fwd, sp.pool, s)
+                if box:
+                    self._zbox_den(st, out, amax, den, B, h, w, s)
             if st.den_kind == "ab":   # second pass: den_n (y and argmax rewritten with the same values)
                 rec["den_n"] = self._buf((li, "den_n"), (B, C, dh, dw))
                 self._conv_fwd(f"conv_fwd_n:{st.name}", sp.fwd, st, True, cur, None, out, amax, rec["den_n"], B, h, w,
@@ -453,6 +486,11 @@ class LRPEngine:
             if sp.bwd == "drsa_amd_first_layer_bwd":
                 self._call(f"first_layer_bwd:{st.name}", sp.bwd, g.data_ptr(), _capi.ptr(amax_in),
                            st.w2_first.data_ptr(), out.data_ptr(), Bq, clones, st.cout, h, w, s)
+            elif sp.bwd == "drsa_amd_first_layer_zbox_bwd":
+                lo, hi, _, _ = self._zbox_maps(st, h, w)
+                self._call(f"first_layer_bwd:{st.name}", sp.bwd, g.data_ptr(), _capi.ptr(amax_in),
+                           st.zb_wpn.data_ptr(), x_in.data_ptr(), lo.data_ptr(), hi.data_ptr(), out.data_ptr(), Bq,
+                           clones, st.cout, h, w, s)
             elif st.den_kind == "ab":
                 # R (ReLU-masked) at the conv output -> gp, gn -> two backward convs -> combine + post
                 n_out = g.numel() // Bq

@@ -105,6 +105,10 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
         code = {(2, 2): 1, (2, 4): 2}.get(st.pool_k, 0) if st.pool and st.proj is None else 0
         if code == 2 and not has_kernel(_FWD + "_has_kernel", st.cin, st.cout, w, st.ng_fwd, 2, int(bf)):
             code = 0
+        if st.den_kind == "box" and code == 2:
+            # the ZBox denominator at a pooled map's argmax is formed for 2x2 cells (drsa_amd_first_layer_zbox_den);
+            # any other pool goes through maxpool_capture, which gathers the full-resolution copy
+            code = 0
         proj = None
         if st.proj is not None or not st.pool:
             # WSquare / Flat without a pool after it (VGGish conv0 -> conv3): the per-sample denominator IS the
@@ -155,6 +159,8 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
             g_in = "unpool"
         if li == 0 and st.den_kind == "map" and st.cin == 1:
             entry = "drsa_amd_first_layer_bwd"
+        elif st.den_kind == "box":      # parse: the first conv, one input channel; g pool-sparse or dense as above
+            entry = "drsa_amd_first_layer_zbox_bwd"
         elif st.den_kind == "ab":       # ab_split, two plain backward convs, ab_combine (which applies post)
             entry = _BWD
         else:

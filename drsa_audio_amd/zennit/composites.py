@@ -103,3 +103,24 @@ class NameLayerMapComposite(Composite):
     def rule_for(self, name: str, module: nn.Module):
         r = self.name_map_composite.rule_for(name, module)
         return r if r is not None else self.layer_map_composite.rule_for(name, module)
+
+
+class EpsilonGammaBox(SpecialFirstLayerMapComposite):
+    """zennit's preset of the same name: ZBox(low, high) on the first convolution, Gamma on the other
+    convolutions, Epsilon on dense layers, Norm on average pools and Pass on activations.  ``layer_map`` /
+    ``first_map`` entries are tried before the preset's own; ``zero_params`` goes to every weighted rule."""
+
+    def __init__(self, low, high, epsilon=1e-6, gamma=0.25, stabilizer=1e-6, layer_map=None, first_map=None,
+                 zero_params=None, canonizers=None):
+        from .rules import Epsilon, Gamma, Norm, Pass, ZBox
+        from .types import Activation, AvgPool, Convolution, Linear
+        layer_map = list(layer_map or []) + [
+            (Activation, Pass()),
+            (AvgPool, Norm(stabilizer=stabilizer)),
+            (Convolution, Gamma(gamma=gamma, stabilizer=stabilizer, zero_params=zero_params)),
+            (Linear, Epsilon(epsilon=epsilon, zero_params=zero_params)),
+        ]
+        first_map = list(first_map or []) + [
+            (Convolution, ZBox(low=low, high=high, stabilizer=stabilizer, zero_params=zero_params)),
+        ]
+        super().__init__(layer_map, first_map, canonizers=canonizers)

@@ -13,7 +13,12 @@ Semantics (reference name maps ``constants.py:27-51``):
                one denominator per set; R_in = α·pos − β·neg (HIP engine: convs with a non-negative
                input; elsewhere compiling the composite raises ``EngineError``)
   Norm(ε)      ≡ Epsilon(ε) on conv/dense layers
-Every rule but AlphaBeta and Pass also compiles on the dense head (``classifier.*``), with the same
+  ZBox(low, high, ε)  for an input in the box low ≤ x ≤ high, l / h = low[:1] / high[:1] spread over x:
+               den = (f(x; W, b) − f(l; W+, b+)) − f(h; W−, b−),  g = R / stab_ε(den),
+               R_in = x ⊙ Jᵀ_W g − l ⊙ Jᵀ_{W+} g − h ⊙ Jᵀ_{W−} g   (b = b+ + b−: the bias cancels in den, so the
+               rule conserves with or without a bias; den ≥ 0 inside the box.  HIP engine: the first conv,
+               one input channel; elsewhere compiling the composite raises ``EngineError``)
+Every rule but AlphaBeta, ZBox and Pass also compiles on the dense head (``classifier.*``), with the same
 semantics on ``f = Linear`` and a signed or non-negative input:
 
   rule      conv trunk                      dense head
@@ -25,7 +30,8 @@ semantics on ``f = Linear`` and a signed or non-negative input:
                                             on ``classifier.0`` only with the last conv's ReLU unmapped
   Flat      yes                             as WSquare
   AlphaBeta non-negative input only         ``EngineError``
-  Pass      activations only                activations only
+  ZBox      first conv, Cin = 1, only       ``EngineError``
+  Pass     activations only                activations only
 ``zero_params`` on a dense layer raises ``EngineError``.
 WSquare / Flat do not multiply by the layer's input, so under a Pass on the ReLU below them relevance
 reaches units with z <= 0.  Inside the head the plan runs that case (the layer below takes unmasked
@@ -100,6 +106,33 @@ class AlphaBeta(BasicHook):
         super().__init__(zero_params)
         self.alpha, self.beta = float(alpha), float(beta)
         self.stabilizer = Stabilizer.ensure(stabilizer).epsilon
+
+
+class ZBox(BasicHook):
+    """zennit ZBox: the first-layer rule for an input bounded by ``low <= x <= high``.
+
+    ``low`` / ``high``: Python floats, or tensors broadcastable to one sample ``[1, 1, H, W]``; a tensor
+    with a batch dimension greater than 1 contributes its first row (zennit's ``low[:1]``).  Inputs
+    outside the box are NOT checked (zennit does not check them either): there the denominator can
+    change sign and the heatmap loses its meaning, silently."""
+    kind = "zbox"
+
+    def __init__(self, low, high, stabilizer=1e-6, zero_params=None):
+        super().__init__(zero_params)
+        self.low, self.high = low, high
+        self.stabilizer = Stabilizer.ensure(stabilizer).epsilon
+
+    def bounds(self, x):
+        """(l, h): both bounds spread over ``x`` (``low[:1].expand_as(x)``), in x's dtype on x's device."""
+        return tuple(_bound(v, x) for v in (self.low, self.high))
+
+
+def _bound(v, x):
+    import torch
+    t = torch.as_tensor(v).detach().to(device=x.device, dtype=x.dtype)
+    if t.dim() == x.dim() and t.size(0) > 1:
+        t = t[:1]
+    return t.expand_as(x)
 
 
 class Norm(BasicHook):

@@ -370,6 +370,29 @@ int drsa_amd_first_layer_bwd(const float* g, const uint8_t* amax, const float* w
 /* Input-independent WSquare / Flat denominator map conv(1; W2, b2): [C][H][W]. */
 int drsa_amd_first_layer_den(const float* w2, const float* b2, float* den, int C, int CI, int H, int W, void* stream);
 
+/* First-layer (one input channel) ZBox rule (zennit 0.5.1 ZBox) for an input in the box low <= x <= high,
+ * W+ = max(W, 0), W- = min(W, 0), b+- likewise; low_img / high_img [H][W] are the bounds spread over one sample.
+ *
+ * The rule's input-independent maps, [C][H][W] each, wp / wn [C][9], bp / bn [C] or NULL:
+ *   zl = conv(low_img; wp) + bp,  zh = conv(high_img; wn) + bn
+ * (zero padding: out-of-image taps are skipped; one fma chain per output, taps (ky, kx) ascending, bias last). */
+int drsa_amd_first_layer_zbox_maps(const float* wp, const float* bp, const float* wn, const float* bn,
+                                   const float* low_img, const float* high_img, float* zl, float* zh, int C, int H,
+                                   int W, void* stream);
+/* The per-sample denominator den = (a - zl[at]) - zh[at], a = the first conv's forward output of an H x W input.
+ * amax != NULL: a, amax, den [B][C][H/2][W/2] (2x2-pooled; at = the cell's argmax pixel, byte = 2 row + col),
+ * even H and W, zl and zh 8-byte aligned.  amax == NULL: a, den [B][C][H][W], at = the pixel itself.  C x H x W must stay below 2^31. */
+int drsa_amd_first_layer_zbox_den(const float* a, const uint8_t* amax, const float* zl, const float* zh, float* den,
+                                  int B, int C, int H, int W, void* stream);
+/* The backward: out[q] = (x[q / clones] - low_img) S+ + (x[q / clones] - high_img) S-, S+- = J^T_{W+-} g[q], each one
+ * fp32 fma chain per pixel in the order (channel, dy, dx); the products and the sum of the epilogue are rounded one
+ * by one.  wpn [2][C][9]: W+ then W-; x [Bq / clones][H][W]; out [Bq][H][W].  g and amax as
+ * drsa_amd_first_layer_bwd: amax != NULL: g pooled (even H, W % 4 == 0; out, x, low_img, high_img 16-byte
+ * aligned); amax == NULL: g dense, any H, W and alignment.  One sample's C x H x W must stay below 2^31. */
+int drsa_amd_first_layer_zbox_bwd(const float* g, const uint8_t* amax, const float* wpn, const float* x,
+                                  const float* low_img, const float* high_img, float* out, int Bq, int clones, int C,
+                                  int H, int W, void* stream);
+
 /* HeatmapGenerator post-processing (explainer.py:99-123, sort_subspaces 151-176): standard
  * heatmap + relevance, subspace heatmaps sorted by descending relevance, relevances, mask
  * (int64, numpy argsort(...)[..., ::-1] order; relevances are numpy's float32 sums).
