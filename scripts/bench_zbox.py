@@ -1,5 +1,5 @@
-"""Times the ZBox first layer's kernels (csrc/first_layer_zbox.hip) next to the WSquare / Flat backward they
-were modelled on, at the headline shape of bench.py: B = 512 samples, 4 relevance clones, C = 32 channels,
+"""Times the ZBox first layer's kernels (csrc/first_layer_zbox.hip; the backward is csrc/first_layer_bwd.h with
+two chains) next to the WSquare / Flat backward (the same kernel with one chain), at the headline shape of bench.py: B = 512 samples, 4 relevance clones, C = 32 channels,
 128 x 128 input, relevance pool-sparse (64 x 64 cells with their argmax bytes).  HIP events, 20 timed
 repeats after warm-up, the kernels alternating in one process (the method of scripts/bench_prca.py;
 DESIGN.md 14):

@@ -149,6 +149,27 @@ def test_bwd_dense_misaligned_g():
     assert torch.equal(out, ref)
 
 
+# dense: scalar loads with partial tiles both ways, float4 loads; pooled: generic width with a partial tile,
+# the W == 128 specialisation with partial tile rows
+@pytest.mark.parametrize("H,W,pooled", [(17, 65, False), (16, 64, False), (6, 136, True), (34, 128, True)])
+def test_bwd_runs_the_chain_of_first_layer_bwd(H, W, pooled):
+    """Non-negative weights (W+ = w2, W- = +0), x = 1, low = 0, high = 1: ZBox returns (1 - 0) S+ + (1 - 1) S-
+    = S+ + 0, and S+ is the chain of drsa_amd_first_layer_bwd on the same g, amax and w2: bit for bit (a
+    signed zero compares equal), both entry points being one kernel with one or two chains."""
+    C, clones = 5, 2
+    rel, amax, x, _, _ = _bwd_inputs(C, H, W, clones, pooled, 500 + H + W)
+    w2 = torch.rand(C, 9, generator=torch.Generator().manual_seed(H * W))
+    wpn = torch.stack([w2, torch.zeros_like(w2)])
+    drel, damax, dw2, dwpn = (_d(t) for t in (rel, amax, w2, wpn))
+    one, lo, hi = torch.ones_like(x), torch.zeros(H, W), torch.ones(H, W)
+    zbox = _bwd_call(drel, damax, dwpn, _d(one), _d(lo), _d(hi), clones, C, H, W)
+    out = torch.full((rel.size(0), 1, H, W), float("nan"), device=DEV)
+    _capi.call("drsa_amd_first_layer_bwd", drel.data_ptr(), _capi.ptr(damax), dw2.data_ptr(), out.data_ptr(),
+               rel.size(0), clones, C, H, W, _capi.stream_ptr(DEV))
+    torch.cuda.synchronize()
+    assert float(out.abs().max().cpu()) > 0 and torch.equal(zbox, out.cpu())
+
+
 # ------------------------------------------------------------------ engine
 def _zmap(nm):
     return [(["features.0"], ZBox(LOW, HIGH, stabilizer=1e-7))] + list(nm[1:])
