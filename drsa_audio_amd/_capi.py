@@ -41,6 +41,15 @@ SIGNATURES = {
     "drsa_amd_drsa_run_batched": (_i32, [_i32, _vp, _i32, _i32, _i32, _vp]),
     "drsa_amd_drsa_partial_bf16": (_i32, [_vp, _vp, _i64, _i32, _i32, _fp, _fp, _vp, _sz, _vp]),
     "drsa_amd_drsa_partial_f16": (_i32, [_vp, _vp, _i64, _i32, _i32, _fp, _fp, _vp, _sz, _vp]),
+    "drsa_amd_drsa_any_supported": (_i32, [_i32, _i32]),
+    "drsa_amd_drsa_any_slab_floats": (_sz, [_i32, _i32]),
+    "drsa_amd_drsa_any_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "drsa_amd_drsa_any_partial": (_i32, [_fp, _fp, _i64, _i32, _i32, _fp, _fp, _vp, _sz, _vp]),
+    "drsa_amd_drsa_any_finish": (_i32, [_fp, _i64, _i32, _i32, _fp, _fp, _fp, _i32, _ip, _vp]),
+    "drsa_amd_drsa_any_finish_counted": (_i32, [_fp, _i64, _i32, _i32, _fp, _fp, _fp, _ip, _vp]),
+    "drsa_amd_drsa_any_step": (_i32, [_fp, _fp, _i64, _i32, _i32, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "drsa_amd_drsa_any_objective": (_i32, [_fp, _fp, _i64, _i32, _i32, _fp, _fp, _vp, _sz, _vp]),
+    "drsa_amd_drsa_any_run": (_i32, [_fp, _fp, _i64, _i32, _i32, _fp, _fp, _i32, _fp, _ip, _vp, _sz, _i32, _vp]),
     "drsa_amd_polar": (_i32, [_fp, _i32, _fp, _ip, _vp]),
     "drsa_amd_subspace_relevances_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "drsa_amd_subspace_relevances": (_i32, [_fp, _fp, _i64, _i64, _i32, _i32, _fp, _fp, _vp, _sz, _vp]),

@@ -30,6 +30,21 @@ Geom geom(int d, int K) {
   return g;
 }
 
+// The natural geometry: any K | d at d <= 128.  Concept blocks sit at their real columns (DKp = dk,
+// no per-block padding, no phantom concepts), DP = pow2ceil(max(16, d)); the slab is
+// gs[i DP + j] = Gt[i][j] (i, j < d), gs[DP DP + k] = S_k (k < K), +0 elsewhere.  The finish
+// kernels take the block stride as a run-time value and work at DKp = dk; the partial is
+// drsa_partial_nat_kernel (the padded partial kernels need power-of-two blocks).
+Geom geom_nat(int d, int K) {
+  Geom g{d, K, 0, 0, 0, 0, false};
+  if (d <= 0 || d > 128 || K <= 0 || d % K) return g;
+  g.dk = g.DKp = d / K;
+  g.DP = pow2ceil(d < 16 ? 16 : d);
+  g.Kp = K;
+  g.ok = true;
+  return g;
+}
+
 inline size_t slab_floats(const Geom& g) { return (size_t)g.DP * g.DP + g.Kp; }
 // per-workgroup slab stride in the workspace: 16-B aligned rows for the float4 reduce
 inline size_t slab_stride(const Geom& g) { return (slab_floats(g) + 3) / 4 * 4; }

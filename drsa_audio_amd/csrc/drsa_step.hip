@@ -26,11 +26,15 @@
 // identity block (polar(diag(V, I)) = diag(polar(V), I)).  E.g. VGGish layer 19 (d = 100, K = 4,
 // getdrsadata.py:119) runs as DP = 128, DKp = 32.  The gradient slab that crosses the ABI (and the
 // all-reduce of the sharded path) is in padded coordinates: drsa_amd_drsa_slab_floats(d, K).
+// That embedding needs DKp <= 64 and K DKp <= 128.  Every other K | d (d = 100 with K = 5, 10, 20;
+// K = 1 at d > 64; ...) runs on the natural geometry -- blocks at their real columns, geom_nat,
+// drsa_partial_nat.h -- through the drsa_amd_drsa_any_* entry points at the end of this file.
 #include "common.h"
 #include "drsa_amd.h"
 #include "polar_ns.h"
 #include "drsa_geom.h"
 #include "drsa_partial.h"
+#include "drsa_partial_nat.h"
 #include "drsa_finish.h"
 #include "drsa_coop.h"
 
@@ -219,8 +223,15 @@ struct ProblemArgs {   // what the needs look at
   int dtype = 0;
 };
 
-int check_problem(const char* who, Geom& g, int d, int K, int64_t N, unsigned need, const ProblemArgs& a = {}) {
-  g = geom(d, K);
+int check_problem(const char* who, Geom& g, int d, int K, int64_t N, unsigned need, const ProblemArgs& a = {},
+                  bool natural = false) {
+  g = natural ? geom_nat(d, K) : geom(d, K);
+  if (natural) {   // the drsa_any_* entry points
+    if (!g.ok) {
+      drsa::set_error("%s: unsupported d=%d K=%d (need 0 < d <= 128 and K | d)", who, d, K);
+      return DRSA_EUNSUPPORTED;
+    }
+  }
   DRSA_REQUIRE(g.ok, "%s: unsupported d=%d K=%d (need d <= 128, K | d, padded concept width <= 64 and "
                "K * padded width <= 128)", who, d, K);
   DRSA_REQUIRE(N > 0 || (N == 0 && (need & kEmptyOk)), "%s: N must be %s 0", who, (need & kEmptyOk) ? ">=" : ">");
@@ -370,6 +381,38 @@ int run_steps(hipStream_t s, int steps, bool use_graph, Pair&& pair, Tail&& tail
   if (done < steps)
     if (int rc = tail()) return rc;
   return final();
+}
+
+// ---------------------------------------------------------------------------
+// the natural geometry (drsa_amd_drsa_any_*): geom_nat, the ragged partial, then the same reduce
+// and finish kernels at block stride DKp = dk
+// ---------------------------------------------------------------------------
+template <int DP>
+int launch_partial_nat(const float* A, const float* C, int64_t N, const Geom& g, const float* U, float* partials,
+                       const PartialPlan& pl, hipStream_t s) {
+  using Cfg = NCfg<DP>;
+  auto kern = (g.d & 3) == 0 ? drsa_partial_nat_kernel<DP, true> : drsa_partial_nat_kernel<DP, false>;
+  DRSA_SMEM(kern, Cfg::lds_bytes);
+  hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(Cfg::NT), Cfg::lds_bytes, s, A, C, N, g.d, g.K, g.dk, U, partials,
+                     pl.rb_total, (int)slab_stride(g));
+  DRSA_LAUNCH_CHECK();
+  return DRSA_OK;
+}
+
+// gs_out = the gradient slab of the N rows at U (N = 0: zeros); arguments already checked
+int any_partial(const float* A, const float* C, int64_t N, const Geom& g, const float* U, float* gs_out, void* ws,
+                hipStream_t s) {
+  if (N == 0) {
+    DRSA_HIP(hipMemsetAsync(gs_out, 0, slab_floats(g) * sizeof(float), s));
+    return DRSA_OK;
+  }
+  const PartialPlan pl = plan_partial(N);
+  float* partials = (float*)ws;
+  const int rc = with_dp(g.DP, [&](auto dp) -> int {
+    return launch_partial_nat<decltype(dp)::value>(A, C, N, g, U, partials, pl, s);
+  });
+  if (rc) return rc;
+  return launch_reduce(partials, pl, g, gs_out, s);
 }
 
 }  // namespace
@@ -750,6 +793,113 @@ int drsa_amd_drsa_run_batched(int P, const drsa_amd_problem_t* probs, int steps,
   // use_graph on the null stream runs the eager pairs here (unlike drsa_run / run_multi).
   // final objective at U_S -> f_traj[steps]; table's destructor synchronises s on every path
   return run_steps(s, steps, use_graph && s, pair, tail, [&] { return launch_phase(0, 1); });
+}
+
+// ---------------------------------------------------------------------------
+// Every K | d at d <= 128 (the natural geometry, geom_nat): fp32 only, no fused step.  Each entry
+// point takes its padded namesake's arguments and also accepts the shapes the padded path takes
+// (its slab layout and summation order differ from the padded ones).
+// ---------------------------------------------------------------------------
+int drsa_amd_drsa_any_supported(int d, int K) { return geom_nat(d, K).ok ? 1 : 0; }
+
+size_t drsa_amd_drsa_any_slab_floats(int d, int K) {
+  const Geom g = geom_nat(d, K);
+  return g.ok ? slab_floats(g) : 0;
+}
+
+size_t drsa_amd_drsa_any_workspace_bytes(int64_t N, int d, int K) {
+  const Geom g = geom_nat(d, K);
+  if (!g.ok || N <= 0) return 0;
+  return ws_bytes(N, g);
+}
+
+int drsa_amd_drsa_any_partial(const float* A, const float* C, int64_t N, int d, int K, const float* U,
+                              float* gs_out, void* ws, size_t ws_size, void* stream) {
+  Geom g;
+  if (int rc = check_problem("drsa_any_partial", g, d, K, N, kEmptyOk | kWs | kAlign, {U, nullptr, ws, ws_size, A, C},
+                             true))
+    return rc;
+  DRSA_REQUIRE(A && C && U && gs_out, "drsa_any_partial: null pointer (d=%d K=%d)", d, K);
+  return any_partial(A, C, N, g, U, gs_out, ws, (hipStream_t)stream);
+}
+
+int drsa_amd_drsa_any_finish(const float* gs, int64_t N_total, int d, int K, const float* U, float* U_out,
+                             float* f_out, int objective_only, int* iters_out, void* stream) {
+  Geom g;
+  if (int rc = check_problem("drsa_any_finish", g, d, K, N_total, objective_only ? 0 : kNoAlias, {U, U_out}, true))
+    return rc;
+  DRSA_REQUIRE(gs && U && f_out && (objective_only || U_out), "drsa_any_finish: null pointer (d=%d K=%d)", d, K);
+  return dispatch_finish(gs, (double)N_total, g, U, U_out, f_out, nullptr, 0, objective_only ? 1 : 0, kPolarTol,
+                         kPolarMaxIter, iters_out, (hipStream_t)stream);
+}
+
+int drsa_amd_drsa_any_finish_counted(const float* gs, int64_t N_total, int d, int K, const float* U, float* U_out,
+                                     float* f_traj, int* counter, void* stream) {
+  Geom g;
+  if (int rc = check_problem("drsa_any_finish_counted", g, d, K, N_total, kNoAlias, {U, U_out}, true)) return rc;
+  DRSA_REQUIRE(gs && U && U_out && f_traj && counter, "drsa_any_finish_counted: null pointer (d=%d K=%d)", d, K);
+  return dispatch_finish(gs, (double)N_total, g, U, U_out, f_traj, counter, 1, 0, kPolarTol, kPolarMaxIter, nullptr,
+                         (hipStream_t)stream);
+}
+
+int drsa_amd_drsa_any_step(const float* A, const float* C, int64_t N, int d, int K, const float* U,
+                           float* U_out, float* f_out, void* ws, size_t ws_size, void* stream) {
+  Geom g;
+  if (int rc = check_problem("drsa_any_step", g, d, K, N, kNoAlias | kWs | kAlign, {U, U_out, ws, ws_size, A, C}, true))
+    return rc;
+  DRSA_REQUIRE(A && C && U && U_out && f_out, "drsa_any_step: null pointer (d=%d K=%d)", d, K);
+  hipStream_t s = (hipStream_t)stream;
+  float* gs = ws_gs(ws, N, g);
+  if (int rc = any_partial(A, C, N, g, U, gs, ws, s)) return rc;
+  return dispatch_finish(gs, (double)N, g, U, U_out, f_out, nullptr, 0, 0, kPolarTol, kPolarMaxIter, nullptr, s);
+}
+
+int drsa_amd_drsa_any_objective(const float* A, const float* C, int64_t N, int d, int K, const float* U,
+                                float* f_out, void* ws, size_t ws_size, void* stream) {
+  Geom g;
+  if (int rc = check_problem("drsa_any_objective", g, d, K, N, kWs | kAlign, {U, nullptr, ws, ws_size, A, C}, true))
+    return rc;
+  DRSA_REQUIRE(A && C && U && f_out, "drsa_any_objective: null pointer (d=%d K=%d)", d, K);
+  hipStream_t s = (hipStream_t)stream;
+  float* gs = ws_gs(ws, N, g);
+  if (int rc = any_partial(A, C, N, g, U, gs, ws, s)) return rc;
+  return dispatch_finish(gs, (double)N, g, U, nullptr, f_out, nullptr, 0, 1, kPolarTol, kPolarMaxIter, nullptr, s);
+}
+
+// drsa_amd_drsa_run for the natural geometry: per step the ragged partial, the slab reduce and the
+// finish (cooperative at DP = 128: drsa_finish_coop_kernel takes the block stride at run time and
+// nowhere needs a power of two), two steps captured into a hipGraph and replayed.
+int drsa_amd_drsa_any_run(const float* A, const float* C, int64_t N, int d, int K, float* U_io, float* U_tmp,
+                          int steps, float* f_traj, int* counter, void* ws, size_t ws_size, int use_graph,
+                          void* stream) {
+  Geom g;
+  if (int rc = check_problem("drsa_any_run", g, d, K, N, kNoAlias | kWs | kAlign, {U_io, U_tmp, ws, ws_size, A, C}, true))
+    return rc;
+  DRSA_REQUIRE(steps >= 0, "drsa_any_run: steps < 0 (d=%d K=%d)", d, K);
+  DRSA_REQUIRE(A && C && U_io && U_tmp && f_traj && counter, "drsa_any_run: null pointer (d=%d K=%d)", d, K);
+  hipStream_t s = (hipStream_t)stream;
+  float* gs = ws_gs(ws, N, g);
+  DRSA_HIP(hipMemsetAsync(counter, 0, sizeof(int), s));
+  CoopXchg* xc = ws_xchg(ws, N, g);
+  if (int rc = coop_reset(xc, s)) return rc;
+  auto one = [&](const float* Uin, float* Uout) -> int {
+    if (int rc = any_partial(A, C, N, g, Uin, gs, ws, s)) return rc;
+    return step_finish(gs, (double)N, g, Uin, Uout, f_traj, counter, xc, s);
+  };
+  auto pair = [&]() -> int {
+    int rc = one(U_io, U_tmp);
+    return rc ? rc : one(U_tmp, U_io);
+  };
+  auto tail = [&]() -> int {
+    if (int rc = one(U_io, U_tmp)) return rc;
+    DRSA_HIP(hipMemcpyAsync(U_io, U_tmp, (size_t)d * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return DRSA_OK;
+  };
+  auto final = [&]() -> int { return one(U_io, nullptr); };   // f(U_S) -> f_traj[steps]
+  const bool capturing = stream_capturing(s);
+  int rc = run_steps(s, steps, use_graph != 0, pair, tail, final);
+  if (rc || capturing || steps == 0) return rc;
+  return coop_check(xc, s, "drsa_any_run");
 }
 
 int drsa_amd_polar(const float* V, int d, float* U_out, int* iters_out, void* stream) {

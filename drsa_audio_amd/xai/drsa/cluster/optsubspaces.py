@@ -8,7 +8,8 @@ problems).  Here the grid of (class, layer, run) tasks is spread over the ranks 
 group (one process per GPU) by longest-processing-time assignment (cost ~ N * padded d^2); each
 rank advances all of its tasks together, <= ``max_joint`` at a time, in one hipGraph per two
 steps (``drsa_run_joint`` -> ``drsa_amd_drsa_run_multi``), so the single-workgroup polar of one
-problem overlaps the partials of the others.  There is no collective on the data path: the only
+problem overlaps the partials of the others.  A ``num_concepts`` the padded kernels refuse (e.g. 5
+on layer 19, d = 100) runs its tasks one after another through ``drsa_run``.  There is no collective on the data path: the only
 exchange is a final ``all_gather_object`` of the per-task objectives.
 
 Every task writes what ``drsa.main`` writes for its run (drsa.py:157-168):
@@ -76,25 +77,43 @@ def assign(tasks: Sequence[Task], world: int) -> List[List[Task]]:
     return out
 
 
+def route_problems(problems, steps: int):
+    """hip_runner's dispatch, on the current stream.  Problems sharing one padded geometry run
+    batched -- one launch per phase for all of them (drsa_run_batched); mixed geometries or 16-bit
+    inputs advance together in one hipGraph of per-problem chains (drsa_run_joint).  Problems the
+    padded geometry refuses (geometry_kind "natural", e.g. num_concepts = 5 on layer 19, d = 100)
+    have no batched or joint form: they run one after another through drsa_run, in task order, and
+    the padded problems among them go the usual way.  Results come back in the order of `problems`."""
+    from .. import drsa as _drsa
+    natural = [_drsa.geometry_kind(A.size(1), K) == "natural" for A, _, _, K in problems]
+    if any(natural):
+        out = [None] * len(problems)
+        for i, (A, C, U0, K) in enumerate(problems):
+            if natural[i]:
+                out[i] = _drsa.drsa_run(A, C, U0, K, steps)
+        rest = [i for i, nat in enumerate(natural) if not nat]
+        if rest:
+            for i, res in zip(rest, route_problems([problems[i] for i in rest], steps)):
+                out[i] = res
+        return out
+    geoms = {_drsa.batched_geometry(A.size(1), K) for A, _, _, K in problems}
+    fp32 = all(A.dtype == torch.float32 for A, _, _, _ in problems)
+    if len(geoms) == 1 and fp32:
+        # the batched partial folds whole groups of drsa_run's fixed 256-leaf row partition
+        # per workgroup, so the fp32 summation order is drsa_run's whatever the workgroup
+        # count, the tasks sharing the launch, the world size or the LPT plan: grid results
+        # equal drsa.main's bit for bit
+        return _drsa.drsa_run_batched(problems, steps)
+    return _drsa.drsa_run_joint(problems, steps)
+
+
 def hip_runner(problems, steps: int):
-    """Product runner.  Problems sharing one padded geometry run batched -- one launch per phase
-    for all of them (drsa_run_batched); mixed geometries or 16-bit inputs advance together in one
-    hipGraph of per-problem chains (drsa_run_joint)."""
-    from ..drsa import batched_geometry, drsa_run_batched, drsa_run_joint
+    """Product runner: route_problems on a side stream."""
     dev = problems[0][0].device
     side = torch.cuda.Stream(dev)             # graph capture needs a non-default stream
     side.wait_stream(torch.cuda.current_stream(dev))
-    geoms = {batched_geometry(A.size(1), K) for A, _, _, K in problems}
-    fp32 = all(A.dtype == torch.float32 for A, _, _, _ in problems)
     with torch.cuda.stream(side):
-        if len(geoms) == 1 and fp32:
-            # the batched partial folds whole groups of drsa_run's fixed 256-leaf row partition
-            # per workgroup, so the fp32 summation order is drsa_run's whatever the workgroup
-            # count, the tasks sharing the launch, the world size or the LPT plan: grid results
-            # equal drsa.main's bit for bit
-            out = drsa_run_batched(problems, steps)
-        else:
-            out = drsa_run_joint(problems, steps)
+        out = route_problems(problems, steps)
     torch.cuda.current_stream(dev).wait_stream(side)
     return out
 

@@ -33,8 +33,14 @@ class HipBackend:
     """libdrsa_amd kernels on the rank's GPU."""
 
     def __init__(self, A: torch.Tensor, C: torch.Tensor, d: int, K: int):
-        from .drsa import DrsaWorkspace, slab_floats
+        from .drsa import DrsaWorkspace, _entry, _natural_unsupported, geometry_kind, slab_floats
         self.A, self.C, self.d, self.K = A, C, d, K
+        # "natural": a problem the padded geometry refuses (drsa_amd_drsa_any_*: fp32, no fused step)
+        self.kind = geometry_kind(d, K)
+        if self.kind == "natural" and A.dtype != torch.float32:
+            raise _natural_unsupported(f"{str(A.dtype).replace('torch.', '')} activation vectors", d, K)
+        self._partial, self._finish, self._finish_counted = (
+            _entry(n, self.kind) for n in ("drsa_amd_drsa_partial", "drsa_amd_drsa_finish", "drsa_amd_drsa_finish_counted"))
         self.ws = DrsaWorkspace(max(A.size(0), 1), d, K, A.device)
         self.gs = torch.empty(slab_floats(d, K), device=A.device, dtype=torch.float32)
         self.f = torch.empty(1, device=A.device, dtype=torch.float32)
@@ -43,24 +49,24 @@ class HipBackend:
         return self.gs.numel()
 
     def partial(self, U: torch.Tensor) -> torch.Tensor:
-        _capi.call("drsa_amd_drsa_partial", self.A.data_ptr(), self.C.data_ptr(), self.A.size(0), self.d, self.K,
+        _capi.call(self._partial, self.A.data_ptr(), self.C.data_ptr(), self.A.size(0), self.d, self.K,
                    U.data_ptr(), self.gs.data_ptr(), self.ws.ptr, self.ws.nbytes, _capi.stream_ptr(U.device))
         return self.gs
 
     def finish(self, gs: torch.Tensor, N_total: int, U: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         U_new = torch.empty_like(U)
-        _capi.call("drsa_amd_drsa_finish", gs.data_ptr(), int(N_total), self.d, self.K, U.data_ptr(),
+        _capi.call(self._finish, gs.data_ptr(), int(N_total), self.d, self.K, U.data_ptr(),
                    U_new.data_ptr(), self.f.data_ptr(), 0, None, _capi.stream_ptr(U.device))
         return U_new, self.f.clone()
 
     def finish_into(self, gs: torch.Tensor, N_total: int, U: torch.Tensor, U_out: torch.Tensor,
                     f_out: torch.Tensor) -> None:
         """finish() into caller-owned buffers (f(U) -> f_out[0])."""
-        _capi.call("drsa_amd_drsa_finish", gs.data_ptr(), int(N_total), self.d, self.K, U.data_ptr(),
+        _capi.call(self._finish, gs.data_ptr(), int(N_total), self.d, self.K, U.data_ptr(),
                    U_out.data_ptr(), f_out.data_ptr(), 0, None, _capi.stream_ptr(U.device))
 
     def fused_supported(self) -> bool:
-        return bool(_capi.load().drsa_amd_drsa_fused_supported(self.d, self.K))
+        return self.kind == "padded" and bool(_capi.load().drsa_amd_drsa_fused_supported(self.d, self.K))
 
     def fused(self, gs: torch.Tensor, N_total: int, U: torch.Tensor, U_out: torch.Tensor, f_out: torch.Tensor,
               gs_out: torch.Tensor) -> None:
@@ -79,11 +85,11 @@ class HipBackend:
 
     def finish_counted(self, gs: torch.Tensor, N_total: int, U: torch.Tensor, U_out: torch.Tensor,
                        f_traj: torch.Tensor, counter: torch.Tensor) -> None:
-        _capi.call("drsa_amd_drsa_finish_counted", gs.data_ptr(), int(N_total), self.d, self.K, U.data_ptr(),
+        _capi.call(self._finish_counted, gs.data_ptr(), int(N_total), self.d, self.K, U.data_ptr(),
                    U_out.data_ptr(), f_traj.data_ptr(), counter.data_ptr(), _capi.stream_ptr(U.device))
 
     def objective(self, gs: torch.Tensor, N_total: int, U: torch.Tensor) -> torch.Tensor:
-        _capi.call("drsa_amd_drsa_finish", gs.data_ptr(), int(N_total), self.d, self.K, U.data_ptr(), None,
+        _capi.call(self._finish, gs.data_ptr(), int(N_total), self.d, self.K, U.data_ptr(), None,
                    self.f.data_ptr(), 1, None, _capi.stream_ptr(U.device))
         return self.f.clone()
 

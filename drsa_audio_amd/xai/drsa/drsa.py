@@ -28,7 +28,7 @@ import torch
 from ... import _capi
 
 __all__ = ["SubspaceOptimizer", "generalized_fmean", "project_grad", "orthogonalize",
-           "objective_fn", "main", "DrsaWorkspace", "slab_floats", "drsa_run_batched"]
+           "objective_fn", "main", "DrsaWorkspace", "slab_floats", "drsa_run_batched", "geometry_kind"]
 
 
 def _dev(device) -> torch.device:
@@ -40,22 +40,44 @@ def _dev(device) -> torch.device:
     return device
 
 
+def geometry_kind(d: int, K: int) -> str:
+    """Which kernel family runs the problem (host only): "padded" where the padded geometry takes
+    it (d/K padded to a power of two <= 64, K * padded width <= 128: the drsa_amd_drsa_* entry
+    points, with the fused, joint, batched and 16-bit forms), "natural" for every other K | d at
+    d <= 128 (drsa_amd_drsa_any_*: fp32, one problem at a time).  Raises for anything else."""
+    lib = _capi.lib()
+    if lib.drsa_amd_drsa_slab_floats(int(d), int(K)) > 0:
+        return "padded"
+    if lib.drsa_amd_drsa_any_supported(int(d), int(K)):
+        return "natural"
+    raise _capi.DrsaAmdError(f"unsupported DRSA problem d={d} K={K} (need 0 < d <= 128 and K | d)")
+
+
+def _entry(name: str, kind: str) -> str:
+    """The entry point of `kind` for a padded entry point's name."""
+    return name if kind == "padded" else name.replace("drsa_amd_drsa_", "drsa_amd_drsa_any_", 1)
+
+
+def _natural_unsupported(what: str, d: int, K: int) -> "_capi.DrsaAmdError":
+    return _capi.DrsaAmdError(f"{what}: unsupported for the DRSA problem d={d} K={K}, which runs on the natural "
+                              "geometry (fp32, one problem at a time: drsa_run / drsa_step / drsa_objective)")
+
+
 def slab_floats(d: int, K: int) -> int:
     """Floats of the [gradient | S] slab exchanged between drsa_partial and drsa_finish (the
     all-reduce payload of a sharded run): d*d + K for power-of-two shapes, padded coordinates
-    otherwise (e.g. 128*128 + 4 for VGGish layer 19, d = 100, K = 4)."""
-    n = _capi.lib().drsa_amd_drsa_slab_floats(int(d), int(K))
-    if n == 0:
-        raise _capi.DrsaAmdError(f"unsupported DRSA problem d={d} K={K} (d <= 128, K | d, d/K padded to a power "
-                                 "of two <= 64 with K * padded width <= 128)")
-    return int(n)
+    otherwise (e.g. 128*128 + 4 for VGGish layer 19, d = 100, K = 4; 128*128 + 5 for K = 5 on the
+    natural geometry)."""
+    fn = getattr(_capi.lib(), _entry("drsa_amd_drsa_slab_floats", geometry_kind(d, K)))
+    return int(fn(int(d), int(K)))
 
 
 class DrsaWorkspace:
     """Device scratch for one (N, d, K) problem: partial slabs, reduced gradient, counters."""
 
     def __init__(self, N: int, d: int, K: int, device: torch.device):
-        nbytes = _capi.lib().drsa_amd_drsa_workspace_bytes(int(N), int(d), int(K))
+        self.kind = geometry_kind(d, K)
+        nbytes = getattr(_capi.lib(), _entry("drsa_amd_drsa_workspace_bytes", self.kind))(int(N), int(d), int(K))
         if nbytes == 0:
             raise _capi.DrsaAmdError(f"unsupported DRSA problem N={N} d={d} K={K}")
         self.N, self.d, self.K = int(N), int(d), int(K)
@@ -76,7 +98,10 @@ class DrsaWorkspace:
     def coop_status(self) -> int:
         """1 if the cooperative finish of the last run on this workspace timed out (U, f NaN from
         that step on), else 0.  drsa_run raises on it by itself; this is for a run the caller
-        captured into its own graph (drsa_amd_drsa_coop_status; synchronises the stream)."""
+        captured into its own graph (drsa_amd_drsa_coop_status; synchronises the stream).  Padded
+        problems only."""
+        if self.kind != "padded":
+            raise _natural_unsupported("DrsaWorkspace.coop_status", self.d, self.K)
         st = ctypes.c_int(0)
         _capi.call("drsa_amd_drsa_coop_status", self.ptr, self.N, self.d, self.K, ctypes.addressof(st),
                    _capi.stream_ptr(self.buf.device))
@@ -95,26 +120,30 @@ def _check_problem(A: torch.Tensor, C: torch.Tensor, U: torch.Tensor, K: int):
         raise ValueError(f"U must be [{d}, {d}]")
     if K <= 0 or d % K != 0:
         raise ValueError("num_concepts must be a positive divisor of d")
+    kind = geometry_kind(d, K)
+    if kind == "natural" and dt != torch.float32:
+        raise _natural_unsupported(f"{str(dt).replace('torch.', '')} activation vectors", d, K)
+    return kind
 
 
 def drsa_objective(A: torch.Tensor, C: torch.Tensor, U: torch.Tensor, K: int,
                    ws: Optional[DrsaWorkspace] = None) -> torch.Tensor:
     """f(U) on device (0-dim fp32 tensor)."""
-    _check_problem(A, C, U, K)
+    kind = _check_problem(A, C, U, K)
     N, d = A.shape
     ws = ws or DrsaWorkspace(N, d, K, A.device)
-    _capi.call("drsa_amd_drsa_objective", A.data_ptr(), C.data_ptr(), N, d, K, U.data_ptr(),
+    _capi.call(_entry("drsa_amd_drsa_objective", kind), A.data_ptr(), C.data_ptr(), N, d, K, U.data_ptr(),
                ws.f.data_ptr(), ws.ptr, ws.nbytes, _capi.stream_ptr(A.device))
     return ws.f[0].clone()
 
 
 def drsa_step(A, C, U, K, ws: Optional[DrsaWorkspace] = None):
     """One optimiser step: returns (U_new, f(U))."""
-    _check_problem(A, C, U, K)
+    kind = _check_problem(A, C, U, K)
     N, d = A.shape
     ws = ws or DrsaWorkspace(N, d, K, A.device)
     U_new = torch.empty_like(U)
-    _capi.call("drsa_amd_drsa_step", A.data_ptr(), C.data_ptr(), N, d, K, U.data_ptr(),
+    _capi.call(_entry("drsa_amd_drsa_step", kind), A.data_ptr(), C.data_ptr(), N, d, K, U.data_ptr(),
                U_new.data_ptr(), ws.f.data_ptr(), ws.ptr, ws.nbytes, _capi.stream_ptr(A.device))
     return U_new, ws.f[0].clone()
 
@@ -122,8 +151,9 @@ def drsa_step(A, C, U, K, ws: Optional[DrsaWorkspace] = None):
 def drsa_run(A, C, U0, K: int, steps: int, ws: Optional[DrsaWorkspace] = None,
              use_graph: bool = True):
     """S steps natively. Returns (U_S, trajectory tensor [S+1] on device).  bf16 / fp16 A, C take
-    the 16-bit MFMA projection path (drsa_run_joint)."""
-    _check_problem(A, C, U0, K)
+    the 16-bit MFMA projection path (drsa_run_joint).  A problem the padded geometry refuses
+    (geometry_kind "natural", e.g. d = 100, K = 5) runs through drsa_amd_drsa_any_run, fp32 only."""
+    kind = _check_problem(A, C, U0, K)
     if A.dtype in (torch.bfloat16, torch.float16):
         return drsa_run_joint([(A, C, U0, K)], steps, use_graph)[0]
     N, d = A.shape
@@ -133,7 +163,7 @@ def drsa_run(A, C, U0, K: int, steps: int, ws: Optional[DrsaWorkspace] = None,
     traj = torch.empty(steps + 1, dtype=torch.float32, device=A.device)
     stream = torch.cuda.current_stream(A.device)
     graph = bool(use_graph) and stream.cuda_stream != 0
-    _capi.call("drsa_amd_drsa_run", A.data_ptr(), C.data_ptr(), N, d, K, U.data_ptr(),
+    _capi.call(_entry("drsa_amd_drsa_run", kind), A.data_ptr(), C.data_ptr(), N, d, K, U.data_ptr(),
                U_tmp.data_ptr(), int(steps), traj.data_ptr(), ws.counter.data_ptr(), ws.ptr,
                ws.nbytes, 1 if graph else 0, stream.cuda_stream)
     return U, traj
@@ -147,7 +177,8 @@ def _pack_problems(problems, steps: int, use_graph: bool, who: str, fp32_only: b
     dev = problems[0][0].device
     keep, structs, outs = [], [], []
     for A, C, U0, K in problems:
-        _check_problem(A, C, U0, K)
+        if _check_problem(A, C, U0, K) == "natural":
+            raise _natural_unsupported(who, A.size(1), K)
         if A.device != dev:
             raise ValueError(f"{who}: all problems must live on one device")
         if fp32_only and A.dtype != torch.float32:

@@ -37,6 +37,9 @@ int drsa_amd_version(void);
  * Supported: d <= 128, d % K == 0, with dk = d/K padded to DKp = next power of two (<= 64)
  * and DP = next power of two >= max(16, K*DKp) <= 128.  d in {16,32,64,128} runs unpadded;
  * e.g. d = 100, K = 4 (VGGish layer 19, getdrsadata.py:119) runs as DP = 128, DKp = 32.
+ * The reference takes every K | d (drsa.py:61-62); the shapes this padded geometry refuses
+ * (DKp > 64 or K*DKp > 128: d = 100 with K = 5, 10 or 20, K = 1 at d > 64, ...) run through the
+ * drsa_amd_drsa_any_* entry points further down.
  * ------------------------------------------------------------------------- */
 
 /* Bytes of device workspace needed by the drsa_* calls below for N rows (0: unsupported). */
@@ -112,6 +115,35 @@ int drsa_amd_drsa_run(const float* A, const float* C, int64_t N, int d, int K, f
  * (same N, d, K): *status_out = 1 if a hand-off timed out (U, f NaN), else 0 (always 0 at d <= 64).
  * Synchronises `stream`; not callable while it is being captured. */
 int drsa_amd_drsa_coop_status(const void* workspace, int64_t N, int d, int K, int* status_out, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * DRSA optimiser for every K | d at d <= 128 (the reference's own domain, drsa.py:61-62).
+ * The natural geometry: concept blocks at their real columns, DP = next power of two >=
+ * max(16, d); the slab is gs[i*DP + j] = Gt[i][j] (i, j < d), gs[DP*DP + k] = S_k (k < K), +0.0
+ * elsewhere: DP*DP + K floats.  fp32 A, C only; no fused step and no run_multi / run_batched
+ * form.  Each entry point takes the arguments of its namesake above and means the same; a slab
+ * or workspace of one family is not valid for the other (drsa_amd_drsa_any_slab_floats /
+ * _any_workspace_bytes size them).  Every valid (d, K) is accepted, those of the padded family
+ * included (the two families' fp32 summation orders differ, so their results agree to rounding,
+ * not bit for bit).  An unsupported (d, K) returns DRSA_EUNSUPPORTED.  drsa_amd_drsa_any_run uses
+ * the cooperative finish at d > 64 and returns DRSA_ETIMEOUT like drsa_amd_drsa_run.
+ * ------------------------------------------------------------------------- */
+int drsa_amd_drsa_any_supported(int d, int K);               /* 1: 0 < d <= 128, K > 0, K | d */
+size_t drsa_amd_drsa_any_slab_floats(int d, int K);          /* DP*DP + K; 0 if unsupported */
+size_t drsa_amd_drsa_any_workspace_bytes(int64_t N, int d, int K);
+int drsa_amd_drsa_any_partial(const float* A, const float* C, int64_t N, int d, int K, const float* U,
+                              float* gs_out, void* workspace, size_t workspace_bytes, void* stream);
+int drsa_amd_drsa_any_finish(const float* gs, int64_t N_total, int d, int K, const float* U, float* U_out,
+                             float* f_out, int objective_only, int* iters_out, void* stream);
+int drsa_amd_drsa_any_finish_counted(const float* gs, int64_t N_total, int d, int K, const float* U, float* U_out,
+                                     float* f_traj, int* counter, void* stream);
+int drsa_amd_drsa_any_step(const float* A, const float* C, int64_t N, int d, int K, const float* U,
+                           float* U_out, float* f_out, void* workspace, size_t workspace_bytes, void* stream);
+int drsa_amd_drsa_any_objective(const float* A, const float* C, int64_t N, int d, int K, const float* U,
+                                float* f_out, void* workspace, size_t workspace_bytes, void* stream);
+int drsa_amd_drsa_any_run(const float* A, const float* C, int64_t N, int d, int K, float* U_io, float* U_tmp,
+                          int steps, float* f_traj, int* counter, void* workspace, size_t workspace_bytes,
+                          int use_graph, void* stream);
 
 /* Test hook: the cooperative finish's spin budget in 100 MHz ticks for launches enqueued from now on
  * (0: give up at the first poll that finds a workgroup missing, with no minimum poll count);
