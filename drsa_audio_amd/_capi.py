@@ -91,6 +91,7 @@ SIGNATURES = {
                                        _f32, _f32, _i32, _vp]),
     "drsa_amd_ab_split": (_i32, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _i64, _f32, _vp]),
     "drsa_amd_ab_combine": (_i32, [_fp, _fp, _f32, _f32, _fp, _fp, _fp, _i32, _i32, _i64, _i32, _f32, _vp]),
+    "drsa_amd_relevance_post": (_i32, [_fp, _fp, _fp, _fp, _i32, _i32, _i64, _i32, _f32, _vp]),
     "drsa_amd_first_layer_bwd": (_i32, [_fp, _vp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "drsa_amd_first_layer_den": (_i32, [_fp, _fp, _fp, _i32, _i32, _i32, _i32, _vp]),
     "drsa_amd_first_layer_zbox_maps": (_i32, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _vp]),

@@ -1,6 +1,7 @@
 // LRP engine kernels that belong to no layer family:
 //   * heatmap split / per-subspace sums / descending sort (explainer.py:99-176)
 //   * AlphaBeta split / combine around two plain backward convs (pf.py:289)
+//   * the post step of a layer as a launch of its own (multi-layer DRSA capture)
 // The dense head is in linear.hip, the ProjectionModel layers in projection.hip, the first-layer
 // backward and its denominator map in first_layer.hip.
 #include "common.h"
@@ -286,6 +287,13 @@ __global__ __launch_bounds__(256) void ab_split_kernel(const float* __restrict__
   }
 }
 
+// The post step of the layer below on one element, as the conv epilogue takes it (lrp_conv_kernel.h): the quotient
+// by the stabilised denominator (POST_DIV; dv is not read otherwise), then the ReLU mask of the layer's input.  No fma.
+__device__ __forceinline__ float post_value(float R, float xv, float dv, int post, float eps) {
+  if (post == POST_DIV) R = div_nb(R, stab(dv, eps));
+  return (xv > 0.f) ? R : 0.f;
+}
+
 __global__ __launch_bounds__(256) void ab_combine_kernel(const float* __restrict__ pos, const float* __restrict__ neg,
                                                          float alpha, float beta, const float* __restrict__ x,
                                                          const float* __restrict__ den, float* __restrict__ out,
@@ -296,12 +304,35 @@ __global__ __launch_bounds__(256) void ab_combine_kernel(const float* __restrict
     const float a = alpha * pos[i];
     const float b = beta * neg[i];
     float R = a - b;
-    if (post != POST_NONE) {
-      const float xv = x[o];
-      if (post == POST_DIV) R = div_nb(R, stab(den[o], eps));
-      R = (xv > 0.f) ? R : 0.f;
-    }
+    if (post != POST_NONE) R = post_value(R, x[o], post == POST_DIV ? den[o] : 0.f, post, eps);
     out[i] = R;
+  }
+}
+
+// ===========================================================================
+// The post step alone (POST_DIV or POST_MASK), for a relevance R that a backward launch wrote raw (POST_NONE) so
+// that it could be kept: out = post(R), R and out [Bq][n] (out may be R), x and den [Bq / clones][n].
+// V4: four elements per thread (n % 4 == 0 and every pointer 16-byte aligned: a group never leaves its row).
+// ===========================================================================
+template <bool V4>
+__global__ __launch_bounds__(256) void relevance_post_kernel(const float* R, const float* __restrict__ x,
+                                                             const float* __restrict__ den, float* out, int64_t n,
+                                                             int clones, int64_t total, int post, float eps) {
+  constexpr int E = V4 ? 4 : 1;
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t * E < total; t += (int64_t)gridDim.x * 256) {
+    const int64_t i = t * E;
+    const int64_t bq = i / n, j = i - bq * n;
+    const int64_t o = (bq / clones) * n + j;
+    if constexpr (V4) {
+      const float4 r = *reinterpret_cast<const float4*>(R + i);
+      const float4 xv = *reinterpret_cast<const float4*>(x + o);
+      const float4 d = post == POST_DIV ? *reinterpret_cast<const float4*>(den + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(out + i) =
+          make_float4(post_value(r.x, xv.x, d.x, post, eps), post_value(r.y, xv.y, d.y, post, eps),
+                      post_value(r.z, xv.z, d.z, post, eps), post_value(r.w, xv.w, d.w, post, eps));
+    } else {
+      out[i] = post_value(R[i], x[o], post == POST_DIV ? den[o] : 0.f, post, eps);
+    }
   }
 }
 
@@ -348,6 +379,24 @@ int drsa_amd_ab_combine(const float* pos, const float* neg, float alpha, float b
   const int64_t total = (int64_t)Bq * n;
   hipLaunchKernelGGL(ab_combine_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, pos, neg, alpha,
                      beta, x, den, out, n, clones, total, post, eps);
+  DRSA_LAUNCH_CHECK();
+  return DRSA_OK;
+}
+
+int drsa_amd_relevance_post(const float* R, const float* x, const float* den, float* out, int Bq, int clones,
+                            int64_t n, int post, float eps, void* stream) {
+  DRSA_REQUIRE(post == POST_DIV || post == POST_MASK, "relevance_post: post must be POST_DIV or POST_MASK");
+  DRSA_REQUIRE(R && x && out && (den || post == POST_MASK), "relevance_post: null pointer");
+  DRSA_REQUIRE(Bq > 0 && clones > 0 && Bq % clones == 0 && n > 0, "relevance_post: bad shape");
+  const int64_t total = (int64_t)Bq * n;
+  const uintptr_t bits = (uintptr_t)R | (uintptr_t)x | (uintptr_t)out | (post == POST_DIV ? (uintptr_t)den : 0);
+  if (n % 4 == 0 && bits % 16 == 0) {
+    hipLaunchKernelGGL(relevance_post_kernel<true>, dim3(ew_grid(total / 4)), dim3(256), 0, (hipStream_t)stream, R, x,
+                       den, out, n, clones, total, post, eps);
+  } else {
+    hipLaunchKernelGGL(relevance_post_kernel<false>, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, R, x,
+                       den, out, n, clones, total, post, eps);
+  }
   DRSA_LAUNCH_CHECK();
   return DRSA_OK;
 }

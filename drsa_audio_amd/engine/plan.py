@@ -36,7 +36,7 @@ from __future__ import annotations
 
 import os
 import weakref
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -44,7 +44,8 @@ import torch.nn as nn
 from .. import _capi
 from .._capi import POST_DIV, POST_DIV_MAP, POST_DIV_RING, POST_NONE, XM_MUL, XM_NONE, XM_SPLIT
 from .parse import ConvStage, DenseStage, EngineError, _bf16r, _pad32, dense_rule_params, parse   # noqa: F401
-from .schedule import ConvStep, _proj_hw, mark_bwd_bf16, schedule   # noqa: F401 (both: names re-exported)
+from .schedule import (ConvStep, _proj_hw, capture_set, capture_stage, mark_bwd_bf16,   # noqa: F401 (names re-exported)
+                       schedule)
 
 # Alternative plan forms, bit-identical to the defaults, that the parity tests switch on to prove it (module
 # attributes, not run-time knobs; an engine reads them once, when it is constructed):
@@ -236,11 +237,16 @@ class LRPEngine:
         self._call(f"first_layer_zbox_den:{st.name}", "drsa_amd_first_layer_zbox_den", a.data_ptr(), _capi.ptr(amax),
                    zl.data_ptr(), zh.data_ptr(), den.data_ptr(), B, st.cout, h, w, s)
 
-    def _schedule(self, *key):
-        """The (conv steps, dense steps) of (B, H, W, capture, stop_after, fanout), made once per key."""
-        if key not in self._schedules:
-            self._schedules[key] = schedule(self.stages, self.dense, *key, bf16=self.bf16, **self._flags)
-        return self._schedules[key]
+    def _schedule(self, *key, taps: Tuple[int, ...] = ()):
+        """The (conv steps, dense steps) of (B, H, W, capture, stop_after, fanout) and the taps, made once per key."""
+        if not taps:
+            if key not in self._schedules:
+                self._schedules[key] = schedule(self.stages, self.dense, *key, bf16=self.bf16, **self._flags)
+            return self._schedules[key]
+        if key + (taps,) not in self._schedules:
+            self._schedules[key + (taps,)] = schedule(self.stages, self.dense, *key, bf16=self.bf16, taps=taps,
+                                                      **self._flags)
+        return self._schedules[key + (taps,)]
 
     # ---------------------------------------------------------------- buffers
     def _buf(self, key, shape, dtype=torch.float32, zero=False):
@@ -268,10 +274,12 @@ class LRPEngine:
                    _capi.ptr(amax), _capi.ptr(den), B, st.cin, st.cout, h, w, ng, pool, s)
 
     @torch.no_grad()
-    def forward(self, x: torch.Tensor, capture: Optional[int] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, capture: Union[None, int, Tuple[int, ...]] = None,
+                taps: Tuple[int, ...] = ()) -> torch.Tensor:
         """Model forward with all LRP state (argmax, denominators) kept on device.  ``capture``:
-        index of a conv stage whose full-resolution ReLU output is kept even though a max-pool
-        follows (the reference's store_hook, preprocessing.py:92-103)."""
+        index of a conv stage, or a tuple of them, whose full-resolution ReLU output is kept even though a
+        max-pool follows (the reference's store_hook, preprocessing.py:92-103).  ``taps``: the taps the
+        backward will be given (a tapped stage leaves its denominator as a per-sample copy)."""
         _capi.require_gpu(x, "input", dtype=None)
         x = x.detach()
         if self.bf16:
@@ -280,10 +288,11 @@ class LRPEngine:
         if x.dim() != 4 or x.size(1) != self.stages[0].cin:
             raise ValueError(f"input must be [B, {self.stages[0].cin}, H, W]")
         B, _, H, W = x.shape
-        conv_steps, dense_steps = self._schedule(B, H, W, capture, None, 0)
+        capture, taps = tuple(capture) if isinstance(capture, (tuple, list)) else capture, tuple(taps)
+        conv_steps, dense_steps = self._schedule(B, H, W, capture, None, 0, taps=taps)
         self._cur_bufs = self._buffers.setdefault(("fwd", B, H, W), {})
         s = _capi.stream_ptr(self.device)
-        state = {"B": B, "stages": [], "key": (B, H, W, capture)}
+        state = {"B": B, "stages": [], "key": (B, H, W, capture), "taps": taps, "tap_rel": {}}
         cur = x
         for li, (st, sp) in enumerate(zip(self.stages, conv_steps)):
             (h, w), (ho, wo), C = sp.hw, sp.out_hw, st.cout
@@ -404,16 +413,22 @@ class LRPEngine:
 
     @torch.no_grad()
     def backward(self, seed: Optional[torch.Tensor] = None, cls: Optional[torch.Tensor] = None,
-                 one_hot: bool = False, fanout: int = 0, stop_after: Optional[int] = None) -> torch.Tensor:
+                 one_hot: bool = False, fanout: int = 0, stop_after: Optional[int] = None,
+                 taps: Tuple[int, ...] = ()) -> torch.Tensor:
         """Relevance at the input.  ``seed`` [B, n_out] (output relevance) or ``cls`` [B] int32 (lrp_output_modifier
         semantics).  ``fanout``: the projection stage emits K+1 clones per sample (HeatmapGenerator path); otherwise
         rows are treated as the reference's replicated batch.  ``stop_after``: stop once the relevance at the OUTPUT
-        of conv stage ``stop_after`` is known and return it (pool resolution when that stage pools)."""
+        of conv stage ``stop_after`` is known and return it (pool resolution when that stage pools).  ``taps``: conv
+        stages above ``stop_after`` (ascending; the forward was given the same) whose output relevance is recorded
+        on the way down, ``self.last["tap_rel"][stage]``: the buffer the launch above wrote without its post step,
+        readable until the next call; drsa_amd_relevance_post then makes the g the walk goes on with."""
         st0 = self.last
         if st0 is None:
             raise RuntimeError("backward() before forward()")
-        B = st0["B"]
-        conv_steps, dense_steps = self._schedule(*st0["key"], stop_after, fanout)
+        B, taps = st0["B"], tuple(taps)
+        if taps != st0["taps"]:
+            raise ValueError(f"backward(taps={taps}) after forward(taps={st0['taps']}): they must be the same")
+        conv_steps, dense_steps = self._schedule(*st0["key"], stop_after, fanout, taps=taps)
         s = _capi.stream_ptr(self.device)
         self._cur_bufs = self._buffers.setdefault(("bwd", B, fanout), {})
         # ---- dense head, top-down ----
@@ -453,6 +468,16 @@ class LRPEngine:
                 return g
             st, sp, rec = self.stages[li], conv_steps[li], st0["stages"][li]
             (h, w), clones, Bq = sp.hw, sp.clones, B * sp.clones
+            if li in taps:
+                # g is the raw relevance at this stage's output; the post step the launch above left out, into a
+                # buffer of its own
+                st0["tap_rel"][li] = g
+                if sp.tap_post != POST_NONE:
+                    gt, (den, eps) = self._buf((li, "tap_g"), tuple(g.shape)), self._post_args(li, sp.tap_post)
+                    self._call(f"tap_post:{st.pool_name if st.pool else st.relu_name}", "drsa_amd_relevance_post",
+                               g.data_ptr(), rec["y"].data_ptr(), _capi.ptr(den), gt.data_ptr(), Bq, clones,
+                               g.numel() // Bq, sp.tap_post, float(eps), s)
+                    g = gt
             amax_in = rec["amax"] if sp.g_in == "sparse" else None
             if sp.g_in == "proj":
                 P = st.proj
@@ -513,15 +538,16 @@ class LRPEngine:
     # ------------------------------------------------------------ DRSA data
     def capture_stage(self, layer_name: str) -> Tuple[int, str]:
         """(stage index, "relu" | "pool") of a trunk module name (features.<layer_idx>)."""
-        for li, st in enumerate(self.stages):
-            if st.relu_name == layer_name:
-                if st.proj is not None:
-                    raise EngineError("engine: capture inside a ProjectionModel layer is not supported")
-                return li, "relu"
-            if st.pool_name == layer_name and st.proj is None:
-                return li, "pool"
-        raise EngineError(f"engine: {layer_name} is not a ReLU or MaxPool2d output of the conv trunk "
-                          "(DRSA data is captured at ReLU/pool outputs, preprocessing.py:60)")
+        return capture_stage(self.stages, layer_name)
+
+    def _captured(self, li: int, where: str, R: torch.Tensor) -> dict:
+        """What capture() returns for the ReLU or the pool of stage ``li``, whose output relevance is ``R``."""
+        st, rec = self.stages[li], self.last["stages"][li]
+        if where == "pool":
+            return {"act": rec["y"], "rel": R, "amax": None, "H": rec["Hout"], "W": rec["Wout"], "C": st.cout,
+                    "ph": 1, "pw": 1}
+        return {"act": rec["a"], "rel": R, "amax": rec["amax"] if st.pool else None, "H": rec["H"], "W": rec["W"],
+                "C": st.cout, "ph": st.pool_k[0], "pw": st.pool_k[1]}
 
     @torch.no_grad()
     def capture(self, x: torch.Tensor, layer_name: str, cls: Optional[torch.Tensor] = None, one_hot: bool = False,
@@ -532,16 +558,28 @@ class LRPEngine:
         li, where = self.capture_stage(layer_name)
         st = self.stages[li]
         out = self.forward(x, capture=li if (where == "relu" and st.pool) else None)
-        rec = self.last["stages"][li]
         if seed_fn is not None:
             R = self.backward(seed=seed_fn(out).contiguous(), stop_after=li)
         else:
             R = self.backward(cls=cls, one_hot=one_hot, stop_after=li)
-        if where == "pool":
-            return {"act": rec["y"], "rel": R, "amax": None, "H": rec["Hout"], "W": rec["Wout"], "C": st.cout,
-                    "ph": 1, "pw": 1}
-        return {"act": rec["a"], "rel": R, "amax": rec["amax"] if st.pool else None, "H": rec["H"], "W": rec["W"],
-                "C": st.cout, "ph": st.pool_k[0], "pw": st.pool_k[1]}
+        return self._captured(li, where, R)
+
+    @torch.no_grad()
+    def capture_many(self, x: torch.Tensor, layer_names: Sequence[str], cls: Optional[torch.Tensor] = None,
+                     one_hot: bool = False, seed_fn=None) -> Dict[str, dict]:
+        """capture() for several layers in one pass: one forward that keeps every named ReLU map, and one LRP
+        backward down to the lowest named layer that records the relevance at each named layer on its way.
+        {name: what capture(x, name) returns}, bit for bit; the tensors are the engine's buffers, valid until its
+        next call."""
+        names = list(layer_names)
+        where, keep, stop, taps = capture_set(self.stages, names)
+        out = self.forward(x, capture=keep, taps=taps)
+        if seed_fn is not None:
+            R = self.backward(seed=seed_fn(out).contiguous(), stop_after=stop, taps=taps)
+        else:
+            R = self.backward(cls=cls, one_hot=one_hot, stop_after=stop, taps=taps)
+        rel = {stop: R, **self.last["tap_rel"]}
+        return {n: self._captured(li, wh, rel[li]) for n, (li, wh) in zip(names, where)}
 
     # -------------------------------------------------------------- heatmaps
     @torch.no_grad()

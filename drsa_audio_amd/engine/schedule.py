@@ -8,7 +8,7 @@ here and nowhere else; ``LRPEngine.forward`` / ``backward`` walk the result, get
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Callable, List, Optional, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple, Union
 
 from .. import _capi
 from .._capi import POST_DIV, POST_DIV_MAP, POST_DIV_RING, POST_MASK, POST_NONE
@@ -57,6 +57,8 @@ class ConvStep:
     wts_bf16: bool = False      # it runs on the stage's bf16 weight set
     post: int = POST_NONE       # its post step: the division / mask of the layer below (stop_after folded in)
     clones: int = 1             # relevance clones per sample in g and below
+    tap_post: int = POST_NONE   # a tapped stage above the lowest tap: the post step taken out of the backward above it
+    #                             (POST_DIV | POST_MASK), which drsa_amd_relevance_post applies once R is recorded
 
 
 @dataclass(frozen=True)
@@ -79,12 +81,50 @@ def _post_of(st: ConvStage, den: str) -> int:
     return {"map": POST_DIV_MAP, "ring": POST_DIV_RING}.get(den, POST_DIV)
 
 
-def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W: int, capture: Optional[int] = None,
-             stop_after: Optional[int] = None, fanout: int = 0, bf16: bool = False, proj_store: bool = False,
-             den_copy: bool = False, pool24_sparse: bool = True, has_kernel: Callable = lib_has_kernel
+def capture_stage(stages: List[ConvStage], layer_name: str) -> Tuple[int, str]:
+    """(stage index, "relu" | "pool") of a trunk module name (features.<layer_idx>)."""
+    for li, st in enumerate(stages):
+        if st.relu_name == layer_name:
+            if st.proj is not None:
+                raise EngineError("engine: capture inside a ProjectionModel layer is not supported")
+            return li, "relu"
+        if st.pool_name == layer_name and st.proj is None:
+            return li, "pool"
+    raise EngineError(f"engine: {layer_name} is not a ReLU or MaxPool2d output of the conv trunk "
+                      "(DRSA data is captured at ReLU/pool outputs, preprocessing.py:60)")
+
+
+def capture_set(stages: List[ConvStage], layer_names: Sequence[str]
+                ) -> Tuple[List[Tuple[int, str]], Tuple[int, ...], int, Tuple[int, ...]]:
+    """One pass for several captured layers: ([(stage, "relu" | "pool") per name], capture, stop_after, taps)
+    as ``schedule`` takes them.  The ReLU and the pool of one stage may both be named (they share the stage's
+    relevance); the same name twice is an error."""
+    names = list(layer_names)
+    if not names:
+        raise ValueError("capture: no layer given")
+    if len(set(names)) != len(names):
+        raise ValueError(f"capture: a layer is named twice in {names}")
+    where = [capture_stage(stages, n) for n in names]
+    tapped = sorted({li for li, _ in where})
+    keep = tuple(li for li in tapped if stages[li].pool and (li, "relu") in where)
+    return where, keep, tapped[0], tuple(tapped[1:])
+
+
+def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W: int,
+             capture: Union[None, int, Tuple[int, ...]] = None, stop_after: Optional[int] = None, fanout: int = 0,
+             bf16: bool = False, proj_store: bool = False, den_copy: bool = False, pool24_sparse: bool = True,
+             has_kernel: Callable = lib_has_kernel, taps: Tuple[int, ...] = ()
              ) -> Tuple[Tuple[ConvStep, ...], Tuple[DenseStep, ...]]:
     """(conv steps, dense steps) of one call form at one input shape.  ``bf16``: the plan's precision; the
-    three flags: plan._PROJ_STORE, _DEN_COPY, _POOL24_SPARSE as the engine read them."""
+    three flags: plan._PROJ_STORE, _DEN_COPY, _POOL24_SPARSE as the engine read them.  ``capture``: the stage, or
+    the stages, whose full-resolution ReLU output the forward keeps.  ``taps``: conv stages above ``stop_after``,
+    ascending, at whose OUTPUT the backward also records the raw relevance: the backward above a tap leaves its
+    post step out, as above ``stop_after``, and the tapped step carries it (``tap_post``)."""
+    keep = () if capture is None else (capture,) if isinstance(capture, int) else tuple(capture)
+    taps = tuple(taps)
+    if list(taps) != sorted(set(taps)) or any(not 0 <= t < len(stages) for t in taps) or \
+            (taps and stop_after is not None and taps[0] <= stop_after):
+        raise ValueError(f"taps {taps} must be conv stages in ascending order, all above stop_after ({stop_after})")
     L, conv, below, (h, w) = len(stages), [], POST_NONE, (H, W)
     for li, st in enumerate(stages):
         ph, pw = st.pool_k if st.pool else (1, 1)
@@ -93,13 +133,14 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
         if h % 2 or w % 4 or h % ph or w % pw:
             raise ValueError(f"{st.name}: feature map {h}x{w} must have an even height, a width divisible by 4 "
                              f"and sides divisible by the pool")
-        if st.den_kind == "ab" and li == capture and st.pool:
+        if st.den_kind == "ab" and li in keep and st.pool:
             raise EngineError("engine: capture at the ReLU of an AlphaBeta conv is not supported")
         bf = bf16 and st.cin > 1
         entry, den = _FWD + ("_bf16" if bf else ""), "none" if st.den_kind is None else "copy"
         # a WSquare / Flat map is read in place of a per-sample copy where the next backward can divide by it
+        # (a tapped stage's division is a launch of its own, which reads the per-sample copy)
         in_place = (st.den_kind == "map" and st.proj is None and li + 1 < L and stages[li + 1].den_kind != "ab"
-                    and not den_copy)
+                    and not den_copy and li not in taps)
         # pools fused into the conv epilogue: 2x2 and 2x4 (code 1 / 2); others, and the capture layer (its
         # full-resolution ReLU output is kept), go through maxpool_capture
         code = {(2, 2): 1, (2, 4): 2}.get(st.pool_k, 0) if st.pool and st.proj is None else 0
@@ -119,7 +160,7 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
             # its right and bottom: every pixel and every 2 x 2 window is on its own there, and the kernel-side
             # buffers (a, h, a', pooled, argmax) keep that size
             proj = None if st.proj is None else (*_proj_hw(h, w), proj_store)
-        elif li == capture or code == 0:
+        elif li in keep or code == 0:
             form, code = "unfused", 0
         else:
             form = "fused"
@@ -136,7 +177,7 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
             conv.append(ConvStep(**step))
             continue
         # ---- the stage's backward: g from above, the post step of the layer below ----
-        post = POST_NONE if stop_after == li - 1 else below_raw
+        post = POST_NONE if (stop_after == li - 1 or li - 1 in taps) else below_raw
         fold = pool24_sparse and st.pool and st.pool_k == (2, 4) and st.den_kind != "ab" and li > 0
         above = next((s.proj for s in stages[li:] if s.proj is not None), None)     # clones start at the projection
         clones = {1: above.K + 1, 2: above.K}.get(int(fanout), 1) if above is not None and above.mask else 1
@@ -175,7 +216,8 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
                 entry = _BWD + ("_den_ring" if post == POST_DIV_RING else "_den_map")
             else:   # a (2,4) pool is folded without the den map only onto the bf16 kernel (bf holds: the same query)
                 entry = _BWD + ("_bf16_pw" if pool_w == 4 else "_bf16" if bf else "")
-        conv.append(ConvStep(g_in=g_in, pool_w=pool_w, bwd=entry, wts_bf16=bf, post=post, clones=clones, **step))
+        conv.append(ConvStep(g_in=g_in, pool_w=pool_w, bwd=entry, wts_bf16=bf, post=post, clones=clones,
+                             tap_post=below if li in taps else POST_NONE, **step))
     head = []
     for di, ds in enumerate(dense):
         rule, eps_r, signed = ds.rp is not None, int(ds.rule_kind == "epsilon"), int(ds.split and not ds.input_nonneg)
@@ -183,5 +225,5 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
             fwd=_LIN + ("_rule_fwd" if ds.split else "_fwd"), bwd=_LIN + ("_rule_bwd" if rule else "_bwd"),
             signed=signed, wn=bool(signed or ds.negden), relu_mask=int(ds.mask), bcast=int(not ds.split),
             zsign=int(ds.rule_kind == "gamma") if rule else eps_r, xmul=int(ds.split) if rule else eps_r,
-            post=POST_NONE if (di > 0 or stop_after == L - 1) else below))
+            post=POST_NONE if (di > 0 or stop_after == L - 1 or L - 1 in taps) else below))
     return tuple(conv), tuple(head)

@@ -10,6 +10,10 @@
 * ``get_vectors_from_maps``    — preprocessing.py:234-256 (its row order, defect D12, kept)
 * ``drsa_training_data``       — preprocess_data + load_and_normalize_data
                                  (getdrsadata.py:47-59) in one call, ready for ``drsa.main``
+* ``get_intermediates`` / ``preprocess_data_layers`` / ``drsa_training_data_layers`` — the same
+                                 for several layers of one model from ONE forward and ONE LRP
+                                 backward per chunk (the reference runs a full pass per layer,
+                                 getdrsadata.py:118-137); equal to one call per layer, bit for bit
 
 The LRP pass runs on the HIP engine and stops at layer j (nothing below it is needed); the
 activation map is kept by the forward, the relevance arrives in pooled form with its argmax,
@@ -19,7 +23,7 @@ HIP kernel behind the C ABI; there is no CPU path.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -76,14 +80,51 @@ def get_intermediate(model: nn.Module, input_batch: torch.Tensor, composite, lay
         cap = eng.capture(xb, name, cls=None if class_idx is None else _class_rows(xb.size(0), class_idx, x.device),
                           one_hot=one_hot_encoded, seed_fn=_seed_fn(class_idx, num_classes, one_hot_encoded))
         acts.append(cap["act"].clone())
-        if cap["amax"] is not None:
-            full = torch.empty_like(cap["act"])
-            _capi.call("drsa_amd_relevance_unpool", cap["rel"].data_ptr(), cap["amax"].data_ptr(), xb.size(0), 1,
-                       cap["C"], cap["H"], cap["W"], cap["ph"], cap["pw"], full.data_ptr(), _capi.stream_ptr(x.device))
-            rels.append(full)
-        else:
-            rels.append(cap["rel"].clone())
+        rels.append(_rel_map(cap, xb.size(0), x.device))
     return torch.cat(acts, 0), torch.cat(rels, 0)
+
+
+def _rel_map(cap: dict, b: int, device) -> torch.Tensor:
+    """The full relevance map of one capture: a pooled relevance goes back through its argmax."""
+    if cap["amax"] is None:
+        return cap["rel"].clone()
+    full = torch.empty_like(cap["act"])
+    _capi.call("drsa_amd_relevance_unpool", cap["rel"].data_ptr(), cap["amax"].data_ptr(), b, 1, cap["C"], cap["H"],
+               cap["W"], cap["ph"], cap["pw"], full.data_ptr(), _capi.stream_ptr(device))
+    return full
+
+
+def _layer_names(model, layers) -> list:
+    names = [_layer_name(model, layer) for layer in layers]
+    if len(set(names)) != len(names):
+        raise ValueError(f"a layer is named twice in {names}")
+    return names
+
+
+def get_intermediates(model: nn.Module, input_batch: torch.Tensor, composite, layers: Sequence, class_idx: int,
+                      attr_batch_size: int = 64, one_hot_encoded: bool = False,
+                      num_classes: Optional[int] = None) -> Dict[object, Tuple[torch.Tensor, torch.Tensor]]:
+    """``{layer: get_intermediate(..., layer, ...)}`` for several layers from one forward and one LRP backward
+    (down to the lowest of them) per chunk.  An engine on the user-hook slow path has no multi-layer pass: there
+    this is one single-layer call per layer."""
+    layers = list(layers)
+    names = _layer_names(model, layers)
+    eng = get_engine(model, composite)
+    if not hasattr(eng, "capture_many"):
+        return {layer: get_intermediate(model, input_batch, composite, layer, class_idx, attr_batch_size,
+                                        one_hot_encoded, num_classes) for layer in layers}
+    x = _as_device_batch(input_batch, None)
+    B = x.size(0)
+    acts, rels = {n: [] for n in names}, {n: [] for n in names}
+    step = B if attr_batch_size is None else max(1, int(attr_batch_size))
+    for i in range(0, B, step):
+        xb = x[i:i + step]
+        cls = None if class_idx is None else _class_rows(xb.size(0), class_idx, x.device)
+        caps = eng.capture_many(xb, names, cls=cls, one_hot=one_hot_encoded, seed_fn=_seed_fn(class_idx, num_classes, one_hot_encoded))
+        for n in names:
+            acts[n].append(caps[n]["act"].clone())
+            rels[n].append(_rel_map(caps[n], xb.size(0), x.device))
+    return {layer: (torch.cat(acts[n], 0), torch.cat(rels[n], 0)) for layer, n in zip(layers, names)}
 
 
 def _layer_name(model, layer) -> str:
@@ -166,6 +207,73 @@ def preprocess_data(model: nn.Module, input_batch, composite, layer_idx: int, cl
         else:
             _vectors(cap, None, H * W, LAYOUT_ROWS, out_a[i:i + b], out_c[i:i + b], b, dev)
     return out_a, out_c
+
+
+def preprocess_data_layers(model: nn.Module, input_batch, composite, layer_idxs: Sequence[int],
+                           class_idx: Optional[int], num_locations: Optional[int] = None,
+                           one_hot_encoded: bool = False, device=None, attr_batch_size: int = 1024,
+                           layout: int = LAYOUT_REFERENCE, num_classes: Optional[int] = None,
+                           group=None) -> Dict[int, Tuple[torch.Tensor, torch.Tensor]]:
+    """``{layer_idx: preprocess_data(..., layer_idx, ...)}`` for several layers, equal bit for bit to one
+    ``preprocess_data`` call per layer in the order of ``layer_idxs``, from one forward and one LRP backward (down
+    to the lowest layer) per ``attr_batch_size`` chunk.
+
+    The global numpy RNG is consumed as those calls consume it: once the first chunk's maps exist, one
+    ``sample_spatial_locations(B_all, (H, W), L)`` per layer, ``layer_idxs[0]`` first.  ``group``, an empty slice
+    and ``num_locations=None`` as in ``preprocess_data``.  An engine on the user-hook slow path has no multi-layer
+    pass: there this is one ``preprocess_data`` call per layer."""
+    layers = list(layer_idxs)
+    names = _layer_names(model, layers)
+    eng = get_engine(model, composite)
+    if not hasattr(eng, "capture_many"):
+        return {layer: preprocess_data(model, input_batch, composite, layer, class_idx, num_locations,
+                                       one_hot_encoded, device, attr_batch_size, layout, num_classes, group)
+                for layer in layers}
+    x = _as_device_batch(input_batch, device)
+    dev = x.device
+    B = x.size(0)
+    off, B_all = (0, B) if group is None else _sample_offset(B, group, dev)
+    if B_all == 0:
+        raise _capi.DrsaAmdError("preprocess_data: empty input batch")
+
+    def capture(xb):
+        return eng.capture_many(xb, names, cls=None if class_idx is None else _class_rows(xb.size(0), class_idx, dev),
+                                one_hot=one_hot_encoded, seed_fn=_seed_fn(class_idx, num_classes, one_hot_encoded))
+
+    out: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
+    if B == 0:
+        # as preprocess_data: one dummy sample gives every layer's geometry, the numpy stream advances over all draws
+        caps = capture(torch.zeros((1,) + tuple(x.shape[1:]), device=dev, dtype=x.dtype))
+        for layer, n in zip(layers, names):
+            C, H, W = caps[n]["C"], caps[n]["H"], caps[n]["W"]
+            if num_locations:
+                sample_spatial_locations(B_all, (H, W), num_locations)
+            shape = (0, C) if num_locations else (0, H * W, C)
+            out[layer] = (torch.empty(shape, device=dev), torch.empty(shape, device=dev))
+        return out
+    idx: Dict[int, torch.Tensor] = {}
+    step = max(1, int(attr_batch_size))
+    for i in range(0, B, step):
+        xb = x[i:i + step]
+        b = xb.size(0)
+        caps = capture(xb)
+        for layer, n in zip(layers, names):
+            cap = caps[n]
+            C, H, W = cap["C"], cap["H"], cap["W"]
+            if layer not in out:        # the first chunk: the layers' draws in the order of layer_idxs
+                if num_locations:
+                    draws = sample_spatial_locations(B_all, (H, W), num_locations)[off:off + B]
+                    idx[layer] = torch.from_numpy(draws.astype(np.int32)).to(dev)
+                shape = (B * num_locations, C) if num_locations else (B, H * W, C)
+                out[layer] = (torch.empty(shape, device=dev), torch.empty(shape, device=dev))
+            out_a, out_c = out[layer]
+            if num_locations:
+                L = int(num_locations)
+                _vectors(cap, idx[layer][i:i + b].contiguous(), L, layout, out_a[i * L:(i + b) * L],
+                         out_c[i * L:(i + b) * L], b, dev)
+            else:
+                _vectors(cap, None, H * W, LAYOUT_ROWS, out_a[i:i + b], out_c[i:i + b], b, dev)
+    return out
 
 
 def compute_context_vectors(activation_vectors: torch.Tensor, relevance_vectors: torch.Tensor) -> torch.Tensor:
@@ -272,3 +380,14 @@ def drsa_training_data(model: nn.Module, input_batch, composite, layer_idx: int,
     A, C = preprocess_data(model, input_batch, composite, layer_idx, class_idx, num_locations, one_hot_encoded,
                            device, attr_batch_size, group=group)
     return normalize_vectors(A, out=A, group=group), normalize_vectors(C, out=C, group=group)
+
+
+def drsa_training_data_layers(model: nn.Module, input_batch, composite, layer_idxs: Sequence[int], class_idx: int,
+                              num_locations: int = 20, one_hot_encoded: bool = False, device=None,
+                              attr_batch_size: int = 1024, group=None) -> Dict[int, Tuple[torch.Tensor, torch.Tensor]]:
+    """``{layer_idx: drsa_training_data(..., layer_idx, ...)}`` from one pass (``preprocess_data_layers``), then
+    ``normalize_vectors`` on A and on C of each layer separately; ``group`` as in ``drsa_training_data``."""
+    data = preprocess_data_layers(model, input_batch, composite, layer_idxs, class_idx, num_locations, one_hot_encoded,
+                                  device, attr_batch_size, group=group)
+    return {layer: (normalize_vectors(A, out=A, group=group), normalize_vectors(C, out=C, group=group))
+            for layer, (A, C) in data.items()}

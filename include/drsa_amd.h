@@ -393,6 +393,16 @@ int drsa_amd_ab_split(const float* g, const float* den_p, const float* den_n, fl
 int drsa_amd_ab_combine(const float* pos, const float* neg, float alpha, float beta, const float* x, const float* den,
                         float* out, int Bq, int clones, int64_t n, int post, float eps, void* stream);
 
+/* The post step of a layer as a launch of its own, for a relevance R that the backward above wrote raw
+ * (post 0) so that it could be kept (multi-layer DRSA capture): R, out [Bq][n] (out may be R), x, den
+ * [Bq / clones][n], x the layer's output.  post 1 (POST_DIV): out = x > 0 ? R / stab(den, eps) : 0;
+ * post 2 (POST_MASK): out = x > 0 ? R : 0 (den may be NULL).  The arithmetic of the conv epilogue's
+ * post step (IEEE division, no fma), so the result equals a backward launched with that post.  float4
+ * loads and stores when n % 4 == 0 and every pointer is 16-byte aligned, scalar ones otherwise (same
+ * values).  Any other post, a NULL pointer or a bad shape: DRSA_EINVAL. */
+int drsa_amd_relevance_post(const float* R, const float* x, const float* den, float* out, int Bq, int clones,
+                            int64_t n, int post, float eps, void* stream);
+
 /* First-layer (one input channel) WSquare / Flat backward: R = J^T_{W2} g.  amax != NULL: g is the
  * pooled relevance (even H, W % 4 == 0, out 16-byte aligned).  amax == NULL: g is dense, any H, W and
  * alignment (float4 loads when W % 4 == 0 and g is 16-byte aligned, scalar loads otherwise; same values). */
