@@ -69,6 +69,8 @@ class ConvStage:
     bias3: torch.Tensor = None
     W2: torch.Tensor = None              # WSquare / Flat: the weights and bias of the denominator map
     b2: torch.Tensor = None
+    wts_w2: torch.Tensor = None          # K x K WSquare / Flat: W2 in the forward layout, bias3 row 1 = b2
+    bias3_w2: torch.Tensor = None
     # AlphaBeta: second forward (W, W-) for den_n, and the two backward weight sets
     wts_fwd_n: torch.Tensor = None
     bias3_n: torch.Tensor = None
@@ -90,6 +92,11 @@ class ConvStage:
     relu_name: Optional[str] = None      # features.<i> of the ReLU after the conv
     pool_name: Optional[str] = None      # features.<i> of the MaxPool2d (None: no pool)
     pool_k: Tuple[int, int] = (2, 2)     # max-pool kernel (= stride); 2x2 is fused into the conv
+    k: Tuple[int, int] = (3, 3)          # conv kernel (kh, kw); other than 3x3: the drsa_amd_convk_* kernels
+
+    @property
+    def generic(self) -> bool:           # not 3x3: no fused pool, no den ring / map, fp32 only
+        return self.k != (3, 3)
 
 
 @dataclass
@@ -179,11 +186,30 @@ def _weights(m, nxt, bn_type, merge_bn: bool, where: str):
     return (*SequentialMergeBatchNorm.fold(W, b, bn), True)
 
 
-def _check_conv(m: nn.Conv2d, name):
-    ok = (tuple(m.kernel_size) == (3, 3) and tuple(m.stride) == (1, 1) and tuple(m.dilation) == (1, 1) and m.groups == 1
-          and (m.padding == "same" or tuple(m.padding) == (1, 1)) and m.padding_mode == "zeros")
+KMAX = 7    # largest conv kernel side (drsa_amd_convk_supported)
+
+
+def _check_conv(m: nn.Conv2d, name) -> Tuple[int, int]:
+    """(kh, kw) of an odd stride-1 'same' zero-padded conv up to 7 x 7; any other conv is refused."""
+    kh, kw = (int(k) for k in m.kernel_size)
+    same = m.padding == "same" or (not isinstance(m.padding, str) and tuple(m.padding) == ((kh - 1) // 2, (kw - 1) // 2))
+    ok = (kh % 2 == 1 and kw % 2 == 1 and max(kh, kw) <= KMAX and tuple(m.stride) == (1, 1)
+          and tuple(m.dilation) == (1, 1) and m.groups == 1 and same and m.padding_mode == "zeros")
     if not ok:
-        raise EngineError(f"engine: features.{name} must be a 3x3 stride-1 'same' zero-padded conv")
+        raise EngineError(f"engine: features.{name} must be a stride-1 'same' zero-padded conv with an odd kernel "
+                          f"up to {KMAX}x{KMAX} (got kernel {kh}x{kw}, stride {tuple(m.stride)}, padding {m.padding!r}, "
+                          f"padding_mode {m.padding_mode!r})")
+    return kh, kw
+
+
+def _convk_supported(kh: int, kw: int, cin: int, cout: int) -> bool:
+    """drsa_amd_convk_supported where the library is built (host code, no GPU); its rule otherwise, so
+    that LRPEngine.check needs no library."""
+    from .. import _capi
+    try:
+        return bool(_capi.lib().drsa_amd_convk_supported(kh, kw, cin, cout))
+    except (_capi.DrsaAmdError, OSError, AttributeError):
+        return kh in (1, 3, 5, 7) and kw in (1, 3, 5, 7) and 1 <= cin <= 1 << 20 and (cout + 31) // 32 <= 65535
 
 
 def _check_pool(m: nn.MaxPool2d):
@@ -219,7 +245,7 @@ def parse(model: nn.Module, composite, bf16: bool = False) -> Tuple[List[ConvSta
             continue
         if not isinstance(m, nn.Conv2d):
             raise EngineError(f"engine: unexpected feature layer features.{name} ({type(m).__name__})")
-        _check_conv(m, name)
+        ksz = _check_conv(m, name)
         W, b, bn = _weights(m, feats[i + 1][1] if i + 1 < n else None, nn.BatchNorm2d, merge_bn, "trunk")
         W, b = _bf16r(W) if bf16 else W, torch.zeros(m.out_channels) if b is None else b
         j = i + 1 + bn
@@ -260,6 +286,16 @@ def parse(model: nn.Module, composite, bf16: bool = False) -> Tuple[List[ConvSta
         if kind == "zbox" and (stages or m.in_channels != 1):
             raise EngineError(f"engine: ZBox on features.{name} is not supported: it is the rule of the first "
                               "conv of a one-channel input (the box bounds the network input)")
+        if ksz != (3, 3):
+            if kind == "zbox":
+                raise EngineError(f"engine: ZBox on features.{name} needs a 3x3 conv (its kernels are 3x3; got "
+                                  f"{ksz[0]}x{ksz[1]})")
+            if bf16:
+                raise EngineError(f"engine: a bf16 plan needs 3x3 convs (features.{name} is {ksz[0]}x{ksz[1]}; the "
+                                  "K x K kernels are fp32)")
+            if not _convk_supported(*ksz, m.in_channels, m.out_channels):
+                raise EngineError(f"engine: no K x K kernel for features.{name} ({ksz[0]}x{ksz[1]}, "
+                                  f"{m.in_channels} -> {m.out_channels} channels)")
         if kind == "alphabeta" and (not prev_nonneg or (pool and pool_k != (2, 2))):
             raise EngineError(f"engine: AlphaBeta on features.{name} needs a non-negative input (not the first "
                               "conv) and a 2x2 or no max-pool after it")
@@ -269,7 +305,7 @@ def parse(model: nn.Module, composite, bf16: bool = False) -> Tuple[List[ConvSta
         stages.append(ConvStage(name=f"features.{name}", cin=m.in_channels, cout=m.out_channels, rule_kind=kind,
                                 eps=_eps_of(rule) if kind else 0.0, pool=pool, proj=proj, input_nonneg=prev_nonneg,
                                 W=W, b=b, rule=rule, den_kind=den_kind, ng_fwd=2 if den_kind == "ab" else 1 + signs,
-                                ng_bwd=max(signs, 1), relu_name=relu_name, pool_name=pool_name, pool_k=pool_k))
+                                ng_bwd=max(signs, 1), relu_name=relu_name, pool_name=pool_name, pool_k=pool_k, k=ksz))
         prev_nonneg = proj is None      # outputs are post-ReLU (pooled) unless a' follows
         i = j
     # classifier

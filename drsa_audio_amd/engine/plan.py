@@ -21,7 +21,9 @@ instead of replicating the batch K+1 times (explainer.py:92).  A dense stage und
 ``drsa_amd_linear_fwd`` and one ``drsa_amd_linear_bwd``; under Gamma / ZPlus its forward also writes the rule's
 denominators (``drsa_amd_linear_rule_fwd``) and under Gamma / ZPlus / WSquare / Flat its backward is one
 ``drsa_amd_linear_rule_bwd`` with a chain per term of R_in (pf.py:18-27, 257-292: the dense rule comes from the
-same rule_mapper as the conv rule).
+same rule_mapper as the conv rule).  A conv whose kernel is not 3x3 (odd sides up to 7, create_model.py:17,58) runs on
+``drsa_amd_convk_fwd`` / ``drsa_amd_convk_bwd`` in the same arithmetic: its pool is a launch of its own, its g dense,
+and the denominators on both of its sides per-sample copies.
 
 Precision: a model whose parameters are bfloat16 (``model.bfloat16()``) compiles a bf16 plan (the
 reference has no bf16 path): every conv weight set (rule-modified, forward and backward) is rounded to bf16, the
@@ -129,12 +131,16 @@ class LRPEngine:
         rnd = _bf16r if self.bf16 else (lambda t: t)
 
         def fwd_layout(*sets):   # [cout][cin][3][3] each -> [ng][9*cin_p][cout_p], row k = ci*9 + ky*3 + kx
+            if st.generic:       # not 3x3: the K x K kernels' layout (fp32 plans only: parse)
+                return _convk_fwd_layout(sets)
             t = torch.zeros(len(sets), cin_p, 3, 3, cout_p, device=dev)
             for i, Wx in enumerate(sets):
                 t[i, :st.cin, :, :, :st.cout] = rnd(Wx).permute(1, 2, 3, 0)
             return t.reshape(len(sets), 9 * cin_p, cout_p)
 
         def bwd_layout(*sets):   # transposed conv as 'same' conv: [ng][9*cout_p][pad32(cin)], flipped taps
+            if st.generic:
+                return _convk_bwd_layout(sets)
             t = torch.zeros(len(sets), cout_p, 3, 3, cin_o, device=dev)
             for i, Wx in enumerate(sets):
                 t[i, :st.cout, :, :, :st.cin] = rnd(Wx).flip(2, 3).permute(0, 2, 3, 1)
@@ -173,7 +179,11 @@ class LRPEngine:
         elif k in ("wsquare", "flat"):
             W2, b2 = (W * W, bd * bd) if k == "wsquare" else (torch.ones_like(W), torch.zeros_like(b))
             st.W2, st.b2, bsets = rnd(W2.contiguous()), b2.contiguous(), [W2]
-            if st.cin == 1:
+            if st.generic:
+                # the map is the K x K forward over an all-ones input: den = chain(1; W2) + b2 (bias row 1)
+                st.wts_w2, st.bias3_w2 = fwd_layout(W2), torch.zeros(3, cout_p, device=dev)
+                st.bias3_w2[1, :st.cout] = b2
+            elif st.cin == 1:
                 st.w2_first = st.W2.reshape(st.cout, 9).contiguous()
         elif k == "zbox":
             # zennit ZBox: (x; W, b), (l; W+, b+), (h; W-, b-).  b = b+ + b- cancels in the denominator, so
@@ -207,6 +217,13 @@ class LRPEngine:
     def _den_map(self, st: ConvStage, H: int, W: int) -> torch.Tensor:
         if (H, W) not in st.den_maps:
             den = st.den_maps[(H, W)] = torch.empty(st.cout, H, W, device=self.device)
+            if st.generic:
+                ones, scratch = torch.ones(1, st.cin, H, W, device=self.device), torch.empty_like(den)
+                _capi.call("drsa_amd_convk_fwd", ones.data_ptr(), st.wts_w2.data_ptr(), st.bias3_w2.data_ptr(), None,
+                           scratch.data_ptr(), den.data_ptr(), 1, st.cin, st.cout, H, W, *st.k, 1,
+                           _capi.stream_ptr(self.device))
+                torch.cuda.current_stream(self.device).synchronize()     # ones / scratch are freed on return
+                return den
             _capi.call("drsa_amd_first_layer_den", st.W2.data_ptr(), st.b2.data_ptr(), den.data_ptr(), st.cout,
                        st.cin, H, W, _capi.stream_ptr(self.device))
         return st.den_maps[(H, W)]
@@ -270,6 +287,9 @@ class LRPEngine:
             wts = st.wts_fwd_n_bf if neg else st.wts_fwd_bf
         else:
             wts = st.wts_fwd_n if neg else st.wts_fwd
+        if st.generic:      # the K x K forward: no pool, so no argmax
+            return self._call(tag, name, cur.data_ptr(), wts.data_ptr(), bias3.data_ptr(), _capi.ptr(den_map),
+                              out.data_ptr(), _capi.ptr(den), B, st.cin, st.cout, h, w, *st.k, ng, s)
         self._call(tag, name, cur.data_ptr(), wts.data_ptr(), bias3.data_ptr(), _capi.ptr(den_map), out.data_ptr(),
                    _capi.ptr(amax), _capi.ptr(den), B, st.cin, st.cout, h, w, ng, pool, s)
 
@@ -333,8 +353,16 @@ class LRPEngine:
                     self._zbox_den(st, out, amax, den, B, h, w, s)
             if st.den_kind == "ab":   # second pass: den_n (y and argmax rewritten with the same values)
                 rec["den_n"] = self._buf((li, "den_n"), (B, C, dh, dw))
-                self._conv_fwd(f"conv_fwd_n:{st.name}", sp.fwd, st, True, cur, None, out, amax, rec["den_n"], B, h, w,
-                               2, sp.pool, s)
+                if sp.form == "unfused":    # a K x K conv under a pool: den_n at full resolution, gathered at the argmax
+                    den_n_full = self._buf((li, "den_n_full"), (B, C, h, w))
+                    rec["den_ab_full"] = (den_full, den_n_full)     # ab_split runs on the unpooled g
+                    self._conv_fwd(f"conv_fwd_n:{st.name}", sp.fwd, st, True, cur, None, a, None, den_n_full, B, h, w, 2,
+                                   0, s)
+                    self._call(f"maxpool:{st.pool_name}", "drsa_amd_maxpool_capture", a.data_ptr(), den_n_full.data_ptr(),
+                               y.data_ptr(), amax.data_ptr(), rec["den_n"].data_ptr(), B, C, h, w, *st.pool_k, s)
+                else:
+                    self._conv_fwd(f"conv_fwd_n:{st.name}", sp.fwd, st, True, cur, None, out, amax, rec["den_n"], B, h, w,
+                                   2, sp.pool, s)
             if st.proj is not None:
                 P, (hk, wk, store) = st.proj, sp.proj
                 # h and a' are recomputed by projection_bwd from a (no HBM round trip); a' is
@@ -398,6 +426,9 @@ class LRPEngine:
         wts = (st.wts_bwd_bf if sp.wts_bf16 else st.wts_bwd).data_ptr()
         x = x_in.data_ptr() if (st.xmode_bwd != XM_NONE or sp.post != POST_NONE) else None
         tag, shape = f"conv_bwd:{st.name}", (Bq, sp.clones, st.cout, st.cin, *sp.hw)
+        if st.generic:      # the K x K backward: dense g, a per-sample den
+            return self._call(tag, sp.bwd, g.data_ptr(), wts, x, _capi.ptr(den), out.data_ptr(), *shape, *st.k,
+                              st.ng_bwd, st.xmode_bwd, sp.post, float(eps), s)
         if sp.bwd.endswith("_den_ring"):
             self._call(tag, sp.bwd, g.data_ptr(), _capi.ptr(amax_in), wts, int(sp.wts_bf16), x, den["den"].data_ptr(),
                        den["den_const4"].data_ptr(), out.data_ptr(), *shape, st.ng_bwd, st.xmode_bwd, float(eps), s)
@@ -520,10 +551,16 @@ class LRPEngine:
                 # R (ReLU-masked) at the conv output -> gp, gn -> two backward convs -> combine + post
                 n_out = g.numel() // Bq
                 gp, gn = (self._buf((li, k), tuple(g.shape)) for k in ("ab_gp", "ab_gn"))
-                self._call(f"ab_split:{st.name}", "drsa_amd_ab_split", g.data_ptr(), rec["den"].data_ptr(),
-                           rec["den_n"].data_ptr(), gp.data_ptr(), gn.data_ptr(), Bq, clones, n_out, float(st.eps), s)
+                # g was unpooled (a K x K conv under a pool): the denominators at full resolution
+                den_p, den_n = rec["den_ab_full"] if sp.g_in == "unpool" else (rec["den"], rec["den_n"])
+                self._call(f"ab_split:{st.name}", "drsa_amd_ab_split", g.data_ptr(), den_p.data_ptr(),
+                           den_n.data_ptr(), gp.data_ptr(), gn.data_ptr(), Bq, clones, n_out, float(st.eps), s)
                 pos, neg = (self._buf((li, k), (Bq, st.cin, h, w)) for k in ("ab_pos", "ab_neg"))
                 for gg, wts, dst in ((gp, st.wts_bwd, pos), (gn, st.wts_bwd_n, neg)):
+                    if st.generic:
+                        self._call(f"conv_bwd:{st.name}", sp.bwd, gg.data_ptr(), wts.data_ptr(), x_in.data_ptr(), None,
+                                   dst.data_ptr(), Bq, clones, st.cout, st.cin, h, w, *st.k, 1, XM_MUL, POST_NONE, 0.0, s)
+                        continue
                     self._call(f"conv_bwd:{st.name}", sp.bwd, gg.data_ptr(), _capi.ptr(amax_in),
                                wts.data_ptr(), x_in.data_ptr(), None, dst.data_ptr(), Bq, clones, st.cout, st.cin, h, w,
                                1, XM_MUL, POST_NONE, 0.0, s)
@@ -627,3 +664,27 @@ def _bf16_layout(wf: torch.Tensor, cin_p: int, cout_p: int) -> torch.Tensor:
     input channel ci = 16*chunk + 8*half + j (drsa_amd_conv_fwd_bf16, include/drsa_amd.h)."""
     t = wf.reshape(wf.size(0), cin_p // 16, 2, 8, 9, cout_p).permute(0, 1, 4, 2, 5, 3)
     return t.to(torch.bfloat16).contiguous()
+
+
+def _convk_fwd_layout(sets: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Forward-shaped weight sets [cout][cin][kh][kw] -> [ng][cin_p * kh * kw][cout_p] fp32, row
+    k = (ci * kh + ky) * kw + kx, cin_p = cin rounded up to 2, cout_p to 32, padding zero
+    (drsa_amd_convk_fwd, include/drsa_amd.h)."""
+    cout, cin, kh, kw = sets[0].shape
+    cin_p, cout_p = (cin + 1) // 2 * 2, _pad32(cout)
+    t = torch.zeros(len(sets), cin_p, kh, kw, cout_p, device=sets[0].device)
+    for i, w in enumerate(sets):
+        t[i, :cin, :, :, :cout] = w.permute(1, 2, 3, 0)
+    return t.reshape(len(sets), cin_p * kh * kw, cout_p).contiguous()
+
+
+def _convk_bwd_layout(sets: Sequence[torch.Tensor]) -> torch.Tensor:
+    """The transposed conv as a 'same' conv over g: [ng][cout_p * kh * kw][cin_p] fp32 with cout_p = cout
+    rounded up to 2 and cin_p = cin to 32, row (co * kh + ky) * kw + kx = w[co][:, kh-1-ky, kw-1-kx]
+    (drsa_amd_convk_bwd)."""
+    cout, cin, kh, kw = sets[0].shape
+    cout_p, cin_p = (cout + 1) // 2 * 2, _pad32(cin)
+    t = torch.zeros(len(sets), cout_p, kh, kw, cin_p, device=sets[0].device)
+    for i, w in enumerate(sets):
+        t[i, :cout, :, :, :cin] = w.flip(2, 3).permute(0, 2, 3, 1)
+    return t.reshape(len(sets), cout_p * kh * kw, cin_p).contiguous()

@@ -15,6 +15,7 @@ from .._capi import POST_DIV, POST_DIV_MAP, POST_DIV_RING, POST_MASK, POST_NONE
 from .parse import ConvStage, DenseStage, EngineError, _pad32
 
 _FWD, _BWD, _LIN = "drsa_amd_conv_fwd", "drsa_amd_conv_bwd", "drsa_amd_linear"
+_FWDK, _BWDK = "drsa_amd_convk_fwd", "drsa_amd_convk_bwd"     # a conv that is not 3x3 (ConvStage.generic)
 
 
 def lib_has_kernel(query: str, *args: int) -> bool:
@@ -137,13 +138,17 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
             raise EngineError("engine: capture at the ReLU of an AlphaBeta conv is not supported")
         bf = bf16 and st.cin > 1
         entry, den = _FWD + ("_bf16" if bf else ""), "none" if st.den_kind is None else "copy"
+        # a conv that is not 3x3 runs on the K x K kernels: no pool in its epilogue, a dense g, and a
+        # per-sample denominator copy on both of its sides (post NONE / DIV / MASK only)
+        if st.generic:
+            entry = _FWDK
         # a WSquare / Flat map is read in place of a per-sample copy where the next backward can divide by it
         # (a tapped stage's division is a launch of its own, which reads the per-sample copy)
         in_place = (st.den_kind == "map" and st.proj is None and li + 1 < L and stages[li + 1].den_kind != "ab"
-                    and not den_copy and li not in taps)
+                    and not den_copy and li not in taps and not st.generic and not stages[li + 1].generic)
         # pools fused into the conv epilogue: 2x2 and 2x4 (code 1 / 2); others, and the capture layer (its
         # full-resolution ReLU output is kept), go through maxpool_capture
-        code = {(2, 2): 1, (2, 4): 2}.get(st.pool_k, 0) if st.pool and st.proj is None else 0
+        code = {(2, 2): 1, (2, 4): 2}.get(st.pool_k, 0) if st.pool and st.proj is None and not st.generic else 0
         if code == 2 and not has_kernel(_FWD + "_has_kernel", st.cin, st.cout, w, st.ng_fwd, 2, int(bf)):
             code = 0
         if st.den_kind == "box" and code == 2:
@@ -178,13 +183,13 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
             continue
         # ---- the stage's backward: g from above, the post step of the layer below ----
         post = POST_NONE if (stop_after == li - 1 or li - 1 in taps) else below_raw
-        fold = pool24_sparse and st.pool and st.pool_k == (2, 4) and st.den_kind != "ab" and li > 0
+        fold = pool24_sparse and st.pool and st.pool_k == (2, 4) and st.den_kind != "ab" and li > 0 and not st.generic
         above = next((s.proj for s in stages[li:] if s.proj is not None), None)     # clones start at the projection
         clones = {1: above.K + 1, 2: above.K}.get(int(fanout), 1) if above is not None and above.mask else 1
         g_in, pool_w, bf = "dense", 2, False
         if st.proj is not None:
             g_in = "proj"
-        elif st.pool and st.pool_k == (2, 2):
+        elif st.pool and st.pool_k == (2, 2) and not st.generic:
             g_in = "sparse"
         elif (fold and st.bwd_bf16 and below_raw != POST_DIV_RING
               and has_kernel(_BWD + "_has_kernel_bf16_pw", st.cout, st.cin, w_in, 4)):
@@ -198,7 +203,9 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
             g_in, pool_w = "sparse", 4
         elif st.pool:
             g_in = "unpool"
-        if li == 0 and st.den_kind == "map" and st.cin == 1:
+        if st.generic:                  # every rule, AlphaBeta's two plain backwards included
+            entry = _BWDK
+        elif li == 0 and st.den_kind == "map" and st.cin == 1:
             entry = "drsa_amd_first_layer_bwd"
         elif st.den_kind == "box":      # parse: the first conv, one input channel; g pool-sparse or dense as above
             entry = "drsa_amd_first_layer_zbox_bwd"

@@ -12,6 +12,11 @@ Module creation order (and therefore PyTorch default initialisation under a
 fixed ``torch.manual_seed``) is identical to the reference; this is pinned by
 ``tests/golden/model_fixture.npz`` (see ``oracle/gen_fixtures.py``).
 
+Reference defect fixed here (next to D6, the hard-coded ``view(-1, 2048)``): the reference's
+``get_out_shape`` takes ``padding = 1`` for ``'same'``, which is the 'same' padding of a 3x3 kernel
+only, so ``VGGType(conv_kernel=(5, 5))`` sizes its classifier for maps that shrink.  ``'same'`` is
+``((kh - 1) // 2, (kw - 1) // 2)`` here; at 3x3 the value is unchanged.
+
 The ``forward`` here is a plain PyTorch forward kept for users who want logits;
 the explanation hot path never calls it — it is compiled into a HIP plan by
 ``drsa_audio_amd.engine``.
@@ -69,13 +74,17 @@ def get_out_shape(input_size=(128, 216), conv_kernel=(3, 3),
                   out_filters: int = 128, padding=1, stride: int = 1,
                   block_depth: int = 2) -> int:
     """Flattened feature size after the conv trunk (same arithmetic as the reference)."""
-    pad = 1 if padding == "same" else (0 if isinstance(padding, str) else int(padding))
+    kh, kw = _pair(conv_kernel)
+    if padding == "same":
+        pad_h, pad_w = (kh - 1) // 2, (kw - 1) // 2
+    else:
+        pad_h = pad_w = 0 if isinstance(padding, str) else int(padding)
     h, w = float(input_size[0]), float(input_size[1])
     for pk in pool_kernels:
         ph, pw = _pair(pk)
         for _ in range(block_depth):
-            h = (h - conv_kernel[0] + 2 * pad) / stride + 1
-            w = (w - conv_kernel[1] + 2 * pad) / stride + 1
+            h = (h - kh + 2 * pad_h) / stride + 1
+            w = (w - kw + 2 * pad_w) / stride + 1
         h = int((h - (ph - 1) - 1) / ph + 1)
         w = int((w - (pw - 1) - 1) / pw + 1)
     return int(h * w * out_filters)

@@ -296,6 +296,31 @@ int drsa_amd_conv_bwd_den_map(const float* g, const uint8_t* g_amax, int pool_w,
  * followed by the dense-g backward (the same MFMA operands). */
 int drsa_amd_conv_bwd_has_kernel_pw(int cin, int cout, int W, int ng, int pool_w);
 
+/* K x K 'same' conv (odd kh, kw in {1, 3, 5, 7}, stride 1, zero padding ((kh-1)/2, (kw-1)/2)) for the
+ * VGG-type model's conv_kernel argument (create_model.py:17,58).  Each output is one fp32 fma chain
+ * from +0 over k = (ci * kh + ky) * kw + kx ascending (a pixel off the image contributes operand 0);
+ * everything after the chain is drsa_amd_conv_fwd at pool = 0 / drsa_amd_conv_bwd with g_amax = NULL,
+ * and at kh = kw = 3 the results are the bits of those entry points.
+ * Weights: [ng][cin_p * kh * kw][cout_p] fp32, row k as above, cin_p = cin rounded up to 2 (the MFMA's
+ * k step), cout_p = cout rounded up to 32, padding zero; bias [3][cout_p].  A backward call names
+ * its channels like drsa_amd_conv_bwd (cin = channels of g) and takes the taps flipped:
+ * row (co * kh + ky) * kw + kx holds w[co][ci][kh-1-ky][kw-1-kx].
+ * drsa_amd_convk_supported (create_model.py:17,58): 1 if the kernels take this geometry; host only. */
+int drsa_amd_convk_supported(int kh, int kw, int cin, int cout);
+/* Floats of a prepared K x K weight tensor (create_model.py:17,58); 0 if unsupported. */
+size_t drsa_amd_convk_weight_floats(int kh, int kw, int cin, int cout, int ng);
+/* Forward K x K conv + bias + ReLU at full resolution and the layer's LRP denominator (out_den
+ * nullable; den_map non-NULL: out_den is the map's copy), ng as drsa_amd_conv_fwd (create_model.py:17,58).
+ * H even, W % 4 == 0. */
+int drsa_amd_convk_fwd(const float* in, const float* wts, const float* bias, const float* den_map, float* out,
+                       float* out_den, int B, int cin, int cout, int H, int W, int kh, int kw, int ng,
+                       void* stream);
+/* Rule backward of a K x K conv over a dense g, with xmode / post (0..2) / clones as drsa_amd_conv_bwd
+ * (create_model.py:17,58). */
+int drsa_amd_convk_bwd(const float* g, const float* wts, const float* x, const float* den, float* out, int Bq,
+                       int clones, int cin, int cout, int H, int W, int kh, int kw, int ng, int xmode, int post,
+                       float eps, void* stream);
+
 /* WSquare / Flat first layer under a 2x2 max-pool, with its denominator map split for the next
  * backward (zennit WSquare/Flat: den = conv(1; W^2, b^2); constants.py:29 puts
  * WSquare on the first layer).  Such a map holds one value per channel on every pixel off its
