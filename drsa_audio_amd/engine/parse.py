@@ -90,9 +90,16 @@ class ConvStage:
     zb_bn: Optional[torch.Tensor] = None
     den_maps: Dict[Tuple[int, int], torch.Tensor] = field(default_factory=dict)
     relu_name: Optional[str] = None      # features.<i> of the ReLU after the conv
-    pool_name: Optional[str] = None      # features.<i> of the MaxPool2d (None: no pool)
-    pool_k: Tuple[int, int] = (2, 2)     # max-pool kernel (= stride); 2x2 is fused into the conv
+    pool_name: Optional[str] = None      # features.<i> of the MaxPool2d / AvgPool2d (None: no pool)
+    pool_k: Tuple[int, int] = (2, 2)     # pool kernel (= stride); a 2x2 max-pool is fused into the conv
     k: Tuple[int, int] = (3, 3)          # conv kernel (kh, kw); other than 3x3: the drsa_amd_convk_* kernels
+    pool_kind: str = "max"               # "max" | "avg" (AvgPool2d: pool_k any pair, never fused, no argmax)
+    pool_rule: Optional[str] = None      # avg: None (the pool's plain gradient) | "epsilon" (Epsilon / Norm on it)
+    pool_eps: float = 0.0                # avg: that rule's stabiliser
+
+    @property
+    def avg(self) -> bool:
+        return self.pool and self.pool_kind == "avg"
 
     @property
     def generic(self) -> bool:           # not 3x3: no fused pool, no den ring / map, fp32 only
@@ -220,6 +227,37 @@ def _check_pool(m: nn.MaxPool2d):
     return (int(ks[0]), int(ks[1]))
 
 
+def _check_avgpool(m: nn.AvgPool2d, name: str) -> Tuple[int, int]:
+    """(ph, pw) of an AvgPool2d with stride = kernel, no padding, floor mode and its own divisor; any other is
+    refused (that the window divides the map is the schedule's check, per input shape)."""
+    ks, pd = (v if isinstance(v, tuple) else (v, v) for v in (m.kernel_size, m.padding))
+    st = ks if m.stride is None else (m.stride if isinstance(m.stride, tuple) else (m.stride, m.stride))
+    if (tuple(ks) != tuple(st) or tuple(pd) != (0, 0) or m.ceil_mode or m.divisor_override is not None
+            or min(ks) < 1):
+        raise EngineError(f"engine: AvgPool2d {name} must have stride = kernel, no padding, ceil_mode=False and no "
+                          f"divisor_override (got kernel {tuple(ks)}, stride {tuple(st)}, padding {tuple(pd)}, "
+                          f"ceil_mode {m.ceil_mode}, divisor_override {m.divisor_override})")
+    return (int(ks[0]), int(ks[1]))
+
+
+def _avgpool_rule(rule, name: str, relu_name: str, relu_rule) -> Tuple[Optional[str], float]:
+    """(pool_rule, pool_eps) of the rule mapped to an average pool: unmapped (its plain gradient), or Epsilon /
+    Norm; anything else, Pass included, is refused."""
+    if rule is None:
+        if relu_rule is not None:
+            # the pool's plain gradient hands relevance to dead pixels (a = 0) of a live window; with Pass on the
+            # ReLU it would pass them, and the conv rules form no [z < 0] branch (the reasoning of the dense
+            # WSquare / Flat refusal below)
+            raise EngineError(f"engine: an unmapped AvgPool2d {name} below a Pass on its block's activation "
+                              f"({relu_name}) is not supported: map the pool to Norm / Epsilon or leave the "
+                              "activation unmapped")
+        return None, 0.0
+    if _kind(rule) != "epsilon":
+        raise EngineError(f"engine: rule {type(rule).__name__} on AvgPool2d {name} is not supported (Norm, Epsilon "
+                          "or no rule)")
+    return "epsilon", _eps_of(rule)
+
+
 def _rule_ok_on_activation(rule):
     if rule is not None and _kind(rule) != "pass":
         raise EngineError(f"engine: rule {type(rule).__name__} on an activation/pool layer is not supported")
@@ -269,12 +307,23 @@ def parse(model: nn.Module, composite, bf16: bool = False) -> Tuple[List[ConvSta
             if r_f is not None and int(r_f.num_concepts) != proj.K:
                 raise EngineError("engine: SubspaceHook num_concepts differs from the projection")
             j += 3
-        pool, pool_name, pool_k = False, None, (2, 2)
+        pool, pool_name, pool_k, pool_kind, pool_rule, pool_eps = False, None, (2, 2), "max", None, 0.0
         if j < n and isinstance(feats[j][1], nn.MaxPool2d):
             pool_k = _check_pool(feats[j][1])
             pool, pool_name = True, f"features.{feats[j][0]}"
             _rule_ok_on_activation(rules.get(pool_name))
             j += 1
+        elif j < n and isinstance(feats[j][1], nn.AvgPool2d):
+            pool, pool_name, pool_kind = True, f"features.{feats[j][0]}", "avg"
+            pool_k = _check_avgpool(feats[j][1], pool_name)
+            if proj is not None:
+                raise EngineError(f"engine: AvgPool2d {pool_name} after a ProjectionModel layer is not supported (the "
+                                  "projection kernels pool by maximum): a MaxPool2d(2) or no pool there")
+            pool_rule, pool_eps = _avgpool_rule(rules.get(pool_name), pool_name, relu_name, rules.get(relu_name))
+            j += 1
+        elif j < n and isinstance(feats[j][1], nn.AdaptiveAvgPool2d):
+            raise EngineError(f"engine: AdaptiveAvgPool2d features.{feats[j][0]} is not supported: use an AvgPool2d "
+                              "whose kernel (= stride) divides the map")
         if proj is not None:
             proj.pool_after = pool
             if pool and pool_k != (2, 2):
@@ -296,6 +345,9 @@ def parse(model: nn.Module, composite, bf16: bool = False) -> Tuple[List[ConvSta
             if not _convk_supported(*ksz, m.in_channels, m.out_channels):
                 raise EngineError(f"engine: no K x K kernel for features.{name} ({ksz[0]}x{ksz[1]}, "
                                   f"{m.in_channels} -> {m.out_channels} channels)")
+        if pool_kind == "avg" and kind in ("alphabeta", "zbox"):
+            raise EngineError(f"engine: {type(rule).__name__} on features.{name}, whose block AvgPool2d {pool_name} "
+                              "pools, is not supported (its kernels take relevance through a max-pool or none)")
         if kind == "alphabeta" and (not prev_nonneg or (pool and pool_k != (2, 2))):
             raise EngineError(f"engine: AlphaBeta on features.{name} needs a non-negative input (not the first "
                               "conv) and a 2x2 or no max-pool after it")
@@ -305,7 +357,8 @@ def parse(model: nn.Module, composite, bf16: bool = False) -> Tuple[List[ConvSta
         stages.append(ConvStage(name=f"features.{name}", cin=m.in_channels, cout=m.out_channels, rule_kind=kind,
                                 eps=_eps_of(rule) if kind else 0.0, pool=pool, proj=proj, input_nonneg=prev_nonneg,
                                 W=W, b=b, rule=rule, den_kind=den_kind, ng_fwd=2 if den_kind == "ab" else 1 + signs,
-                                ng_bwd=max(signs, 1), relu_name=relu_name, pool_name=pool_name, pool_k=pool_k, k=ksz))
+                                ng_bwd=max(signs, 1), relu_name=relu_name, pool_name=pool_name, pool_k=pool_k, k=ksz,
+                                pool_kind=pool_kind, pool_rule=pool_rule, pool_eps=pool_eps))
         prev_nonneg = proj is None      # outputs are post-ReLU (pooled) unless a' follows
         i = j
     # classifier

@@ -5,7 +5,7 @@ Here the sequential VGG structure (create_model.py:8-97, optionally with the Pro
 modify_model.py:19-60) is compiled into *stages*:
 
   ConvStage   Conv2d [+BN folded by SequentialMergeBatchNorm] -> ReLU
-              [-> Projection/SubspaceFilter/InvProjection] [-> MaxPool2d(2)]
+              [-> Projection/SubspaceFilter/InvProjection] [-> MaxPool2d(k) | AvgPool2d(k)]
   DenseStage  Linear [+BN folded] [-> ReLU] [-> Dropout]
 
 in three steps: parse (parse.py, host only: the stages and every structural refusal), prepare (here, once per plan:
@@ -23,7 +23,10 @@ denominators (``drsa_amd_linear_rule_fwd``) and under Gamma / ZPlus / WSquare / 
 ``drsa_amd_linear_rule_bwd`` with a chain per term of R_in (pf.py:18-27, 257-292: the dense rule comes from the
 same rule_mapper as the conv rule).  A conv whose kernel is not 3x3 (odd sides up to 7, create_model.py:17,58) runs on
 ``drsa_amd_convk_fwd`` / ``drsa_amd_convk_bwd`` in the same arithmetic: its pool is a launch of its own, its g dense,
-and the denominators on both of its sides per-sample copies.
+and the denominators on both of its sides per-sample copies.  A stage that ends in AvgPool2d(k) runs
+its conv at full resolution, then ``drsa_amd_avgpool_fwd``; on the way back one ``drsa_amd_avgpool_bwd`` takes the raw
+relevance at the pool's output through the pool's rule, the ReLU mask and the conv rule's division to a dense g
+(DESIGN 18).
 
 Precision: a model whose parameters are bfloat16 (``model.bfloat16()``) compiles a bf16 plan (the
 reference has no bf16 path): every conv weight set (rule-modified, forward and backward) is rounded to bf16, the
@@ -312,19 +315,19 @@ class LRPEngine:
         conv_steps, dense_steps = self._schedule(B, H, W, capture, None, 0, taps=taps)
         self._cur_bufs = self._buffers.setdefault(("fwd", B, H, W), {})
         s = _capi.stream_ptr(self.device)
-        state = {"B": B, "stages": [], "key": (B, H, W, capture), "taps": taps, "tap_rel": {}}
+        state = {"B": B, "stages": [], "key": (B, H, W, capture), "taps": taps, "tap_rel": {}, "avg_rel": {}}
         cur = x
         for li, (st, sp) in enumerate(zip(self.stages, conv_steps)):
             (h, w), (ho, wo), C = sp.hw, sp.out_hw, st.cout
             den_map = self._den_map(st, h, w) if st.den_kind == "map" else None
             # the stage's buffers: the full-resolution map a (every form but the fused pool), the pooled
             # y with its argmax bytes, and the denominator the schedule says the stage leaves
-            dh, dw = (h, w) if sp.form == "full" else (ho, wo)
+            dh, dw = (h, w) if sp.form in ("full", "avg") else (ho, wo)
             a = self._buf((li, "a"), (B, C, h, w)) if sp.form != "fused" else None
             y = amax = den = None
             if sp.form != "full":
                 y = self._buf((li, "y"), (B, C, ho, wo))
-                amax = self._buf((li, "amax"), (B, C, ho, wo), torch.uint8)
+                amax = self._buf((li, "amax"), (B, C, ho, wo), torch.uint8) if sp.form != "avg" else None
             if sp.den == "ring":
                 den = self._buf((li, "den_ring"), (B, C, 2 * (w // 2) + 8 * (h // 2 - 2)))
             elif sp.den == "copy":
@@ -334,7 +337,13 @@ class LRPEngine:
                    "den": den, "den_map": den_map}
             # ZBox: the conv leaves no denominator; drsa_amd_first_layer_zbox_den forms it from the conv's output
             box = st.den_kind == "box" and den is not None
-            if sp.form == "unfused":
+            if sp.form == "avg":
+                # the conv at full resolution with its denominator there (or the shared map, which is not copied),
+                # then the average pool on its own: no argmax, nothing gathered
+                self._conv_fwd(tag, sp.fwd, st, False, cur, den_map, a, None, den, B, h, w, st.ng_fwd, 0, s)
+                self._call(f"avgpool:{st.pool_name}", "drsa_amd_avgpool_fwd", a.data_ptr(), y.data_ptr(), B, C, h, w,
+                           *st.pool_k, s)
+            elif sp.form == "unfused":
                 den_full = self._buf((li, "den_full"), (B, C, h, w)) if den is not None else None
                 self._conv_fwd(tag, sp.fwd, st, False, cur, den_map, a, None, None if box else den_full, B, h, w,
                                st.ng_fwd, 0, s)
@@ -442,6 +451,23 @@ class LRPEngine:
             self._call(tag, sp.bwd, g.data_ptr(), _capi.ptr(amax_in), wts, x, _capi.ptr(den), out.data_ptr(), *shape,
                        st.ng_bwd, st.xmode_bwd, sp.post, float(eps), s)
 
+    def _unavg(self, li: int, sp: ConvStep, R_y: torch.Tensor, s) -> torch.Tensor:
+        """The way back through the average pool of stage ``li``: from the raw relevance at the pool's output to the
+        dense g of the stage's conv backward (the pool's rule, the ReLU mask, the conv rule's own division), and the
+        relevance at the ReLU's output when that is captured (``self.last["avg_rel"][li]``), in one launch."""
+        st, rec = self.stages[li], self.last["stages"][li]
+        (h, w), Bq = sp.hw, R_y.size(0)
+        g = self._buf((li, "g_unavg"), (Bq, st.cout, h, w))
+        rel = self._buf((li, "rel_full"), (Bq, st.cout, h, w)) if sp.rel_full else None
+        den = rec["den_map"] if sp.den == "map" else rec["den"]
+        self._call(f"avgpool_bwd:{st.pool_name}", "drsa_amd_avgpool_bwd", R_y.data_ptr(), rec["y"].data_ptr(),
+                   rec["a"].data_ptr(), _capi.ptr(den), int(sp.den == "map"), int(st.pool_rule is not None),
+                   float(st.pool_eps), float(st.eps), g.data_ptr(), _capi.ptr(rel), Bq, Bq // self.last["B"], st.cout,
+                   h, w, *st.pool_k, s)
+        if rel is not None:
+            self.last["avg_rel"][li] = rel
+        return g
+
     @torch.no_grad()
     def backward(self, seed: Optional[torch.Tensor] = None, cls: Optional[torch.Tensor] = None,
                  one_hot: bool = False, fanout: int = 0, stop_after: Optional[int] = None,
@@ -496,6 +522,8 @@ class LRPEngine:
         g = R.reshape(B, self.stages[-1].cout, *conv_steps[-1].out_hw)
         for li in range(L - 1, -1, -1):
             if stop_after is not None and li == stop_after:
+                if conv_steps[li].rel_full:     # the captured ReLU of an average-pooled stage: its relevance is the
+                    self._unavg(li, conv_steps[li], g, s)       # pool backward's by-product
                 return g
             st, sp, rec = self.stages[li], conv_steps[li], st0["stages"][li]
             (h, w), clones, Bq = sp.hw, sp.clones, B * sp.clones
@@ -530,6 +558,8 @@ class LRPEngine:
                 if rec["pad"]:
                     G.copy_(Gk[:, :, :h, :w])
                 g = G
+            elif sp.g_in == "unavg":
+                g = self._unavg(li, sp, g, s)
             elif sp.g_in == "unpool":
                 gf = self._buf((li, "g_unpool"), (Bq, st.cout, h, w))
                 self._call(f"maxpool_bwd:{st.pool_name}", "drsa_amd_relevance_unpool", g.data_ptr(),
@@ -583,6 +613,9 @@ class LRPEngine:
         if where == "pool":
             return {"act": rec["y"], "rel": R, "amax": None, "H": rec["Hout"], "W": rec["Wout"], "C": st.cout,
                     "ph": 1, "pw": 1}
+        if st.avg:      # the relevance at the ReLU above an average pool is dense: drsa_amd_avgpool_bwd wrote it
+            return {"act": rec["a"], "rel": self.last["avg_rel"][li], "amax": None, "H": rec["H"], "W": rec["W"],
+                    "C": st.cout, "ph": 1, "pw": 1}
         return {"act": rec["a"], "rel": R, "amax": rec["amax"] if st.pool else None, "H": rec["H"], "W": rec["W"],
                 "C": st.cout, "ph": st.pool_k[0], "pw": st.pool_k[1]}
 

@@ -44,15 +44,19 @@ class ConvStep:
     hw: Tuple[int, int]         # the conv's map
     out_hw: Tuple[int, int]     # the stage output (after projection and pool)
     form: str                   # "fused" (pool in the conv epilogue) | "unfused" (conv, then maxpool_capture) | "full"
-    #                             (no pool in the conv: none follows, or the projection comes first)
+    #                             (no pool in the conv: none follows, or the projection comes first) | "avg" (conv at
+    #                             full resolution with its denominator, then drsa_amd_avgpool_fwd)
     fwd: str                    # conv forward entry point
     pool: int                   # its pool code: 0, 1 (2x2), 2 (2x4)
-    den: str                    # left for the division below: "none" | "copy" (per sample, at the argmax) | "ring"
+    den: str                    # left for the division below: "none" | "copy" (per sample, at the argmax; "full" and
+    #                             "avg": at every pixel) | "ring"
     #                             (compact border ring + the map's interior value) | "map" (the shared map itself)
     proj: Optional[Tuple[int, int, bool]] = None    # projection stage: its kernels' map size (padded when != hw),
     #                             and whether projection_fwd stores h and a' for projection_bwd
     g_in: str = "dense"         # backward: g arrives "dense" | "sparse" (pooled, with argmax bytes) | through "unpool"
-    #                             (drsa_amd_relevance_unpool first) | from "proj" (drsa_amd_projection_bwd first)
+    #                             (drsa_amd_relevance_unpool first) | from "proj" (drsa_amd_projection_bwd first) |
+    #                             through "unavg" (drsa_amd_avgpool_bwd first: the raw relevance at the pool's output
+    #                             in, the stage's own division included: the launch above runs without a post step)
     pool_w: int = 2             # pool width of a sparse g (4: the folded (2,4) pool)
     bwd: Optional[str] = None   # backward entry point (None: at or below stop_after, not run)
     wts_bf16: bool = False      # it runs on the stage's bf16 weight set
@@ -60,6 +64,8 @@ class ConvStep:
     clones: int = 1             # relevance clones per sample in g and below
     tap_post: int = POST_NONE   # a tapped stage above the lowest tap: the post step taken out of the backward above it
     #                             (POST_DIV | POST_MASK), which drsa_amd_relevance_post applies once R is recorded
+    rel_full: bool = False      # an average-pooled stage whose ReLU output is captured: drsa_amd_avgpool_bwd also writes
+    #                             the relevance at that output (the stage at stop_after included)
 
 
 @dataclass(frozen=True)
@@ -91,7 +97,7 @@ def capture_stage(stages: List[ConvStage], layer_name: str) -> Tuple[int, str]:
             return li, "relu"
         if st.pool_name == layer_name and st.proj is None:
             return li, "pool"
-    raise EngineError(f"engine: {layer_name} is not a ReLU or MaxPool2d output of the conv trunk "
+    raise EngineError(f"engine: {layer_name} is not a ReLU or MaxPool2d / AvgPool2d output of the conv trunk "
                       "(DRSA data is captured at ReLU/pool outputs, preprocessing.py:60)")
 
 
@@ -148,7 +154,8 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
                     and not den_copy and li not in taps and not st.generic and not stages[li + 1].generic)
         # pools fused into the conv epilogue: 2x2 and 2x4 (code 1 / 2); others, and the capture layer (its
         # full-resolution ReLU output is kept), go through maxpool_capture
-        code = {(2, 2): 1, (2, 4): 2}.get(st.pool_k, 0) if st.pool and st.proj is None and not st.generic else 0
+        fusable = st.pool and not st.avg and st.proj is None and not st.generic
+        code = {(2, 2): 1, (2, 4): 2}.get(st.pool_k, 0) if fusable else 0
         if code == 2 and not has_kernel(_FWD + "_has_kernel", st.cin, st.cout, w, st.ng_fwd, 2, int(bf)):
             code = 0
         if st.den_kind == "box" and code == 2:
@@ -165,6 +172,11 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
             # its right and bottom: every pixel and every 2 x 2 window is on its own there, and the kernel-side
             # buffers (a, h, a', pooled, argmax) keep that size
             proj = None if st.proj is None else (*_proj_hw(h, w), proj_store)
+        elif st.avg:
+            # an average pool is a launch of its own on the full-resolution map, and the stage's denominator stays
+            # at full resolution for drsa_amd_avgpool_bwd: the shared WSquare / Flat map itself where the 3x3
+            # forward can leave it (the K x K forward writes its per-sample copy)
+            form, den = "avg", "map" if st.den_kind == "map" and not st.generic else den
         elif li in keep or code == 0:
             form, code = "unfused", 0
         else:
@@ -176,19 +188,26 @@ def schedule(stages: List[ConvStage], dense: List[DenseStage], B: int, H: int, W
             if in_place and code == 1 and st.cin == 1 and w % 16 == 0 and h >= 4:
                 entry, den = _FWD + "_den_ring", "ring"
         step = dict(hw=(h, w), out_hw=(h // ph, w // pw), form=form, fwd=entry, pool=code, den=den, proj=proj)
+        if st.avg and li in keep:
+            step["rel_full"] = True
         w_in, (h, w) = w, step["out_hw"]
-        below_raw, below = below, _post_of(st, den)     # the post step of the layer below; this stage's, for the next
+        # the post step of the layer below; this stage's, for the next (none above an average pool, as above a tap:
+        # drsa_amd_avgpool_bwd takes the raw relevance at the pool's output)
+        below_raw, below = below, POST_NONE if st.avg else _post_of(st, den)
         if stop_after is not None and li <= stop_after:
             conv.append(ConvStep(**step))
             continue
         # ---- the stage's backward: g from above, the post step of the layer below ----
         post = POST_NONE if (stop_after == li - 1 or li - 1 in taps) else below_raw
-        fold = pool24_sparse and st.pool and st.pool_k == (2, 4) and st.den_kind != "ab" and li > 0 and not st.generic
+        fold = (pool24_sparse and st.pool and not st.avg and st.pool_k == (2, 4) and st.den_kind != "ab" and li > 0
+                and not st.generic)
         above = next((s.proj for s in stages[li:] if s.proj is not None), None)     # clones start at the projection
         clones = {1: above.K + 1, 2: above.K}.get(int(fanout), 1) if above is not None and above.mask else 1
         g_in, pool_w, bf = "dense", 2, False
         if st.proj is not None:
             g_in = "proj"
+        elif st.avg:
+            g_in = "unavg"
         elif st.pool and st.pool_k == (2, 2) and not st.generic:
             g_in = "sparse"
         elif (fold and st.bwd_bf16 and below_raw != POST_DIV_RING

@@ -98,9 +98,11 @@ def num_flat_features(x: torch.Tensor) -> int:
 
 
 class VGGType(nn.Module):
-    """Configurable VGG-style CNN: ``features`` (conv blocks + max-pool) and ``classifier``.
+    """Configurable VGG-style CNN: ``features`` (conv blocks + pool) and ``classifier``.
 
-    Same argument names and defaults as the reference constructor.
+    Same argument names and defaults as the reference constructor.  ``pool`` (not in the reference): ``"max"``
+    (``nn.MaxPool2d``, the reference's trunk) or ``"avg"`` (``nn.AvgPool2d`` with the same ``pool_kernels``).  A pool
+    has no parameters, so initialisation under a seed does not depend on it.
     """
 
     def __init__(self, n_filters: Sequence[int] = (32, 64, 96, 128),
@@ -109,17 +111,19 @@ class VGGType(nn.Module):
                  n_dense: int = 512, n_classes: int = 10, dropout: float = 0.2,
                  block_depth: int = 2, dense_depth: int = 2,
                  input_size=(128, 256), padding="same", stride: int = 1,
-                 conv_bn: bool = True, dense_bn: bool = True) -> None:
+                 conv_bn: bool = True, dense_bn: bool = True, pool: str = "max") -> None:
         super().__init__()
         if len(n_filters) != len(pool_kernels):
             raise ValueError("number of conv blocks and max-pool kernels must match")
+        if pool not in ("max", "avg"):
+            raise ValueError(f"pool must be 'max' or 'avg', got {pool!r}")
         trunk: List[nn.Module] = []
         prev = 1
         for width, pk in zip(n_filters, pool_kernels):
             trunk += get_conv_block_layers(prev, width, block_depth=block_depth,
                                            kernel=conv_kernel, stride=stride,
                                            padding=padding, conv_bn=conv_bn)
-            trunk.append(nn.MaxPool2d(pk))
+            trunk.append(nn.MaxPool2d(pk) if pool == "max" else nn.AvgPool2d(pk))
             prev = width
         self.features = nn.Sequential(*trunk)
         flat = get_out_shape(input_size=input_size, conv_kernel=conv_kernel,

@@ -558,6 +558,28 @@ int drsa_amd_maxpool_capture(const float* a, const float* den, float* y, uint8_t
 int drsa_amd_relevance_unpool(const float* rel, const uint8_t* amax, int Bq, int clones, int C, int H, int W, int ph,
                               int pw, float* out, void* stream);
 
+/* ph x pw average pool (stride = kernel, no padding) of a full-resolution ReLU output a [B][C][H][W] into
+ * y [B][C][H/ph][W/pw]: y = s / float(ph * pw), s one fp32 chain from 0 over the window in row-major order
+ * (rows outer, columns inner), then one IEEE division: torch's CPU avg_pool2d, bit for bit.  Any window
+ * that divides the map, the whole map included (a chain per output, never a tree).  float4 loads when pw is
+ * 1, 2 or 4, W % 4 == 0 and both pointers are 16-byte aligned; scalar ones otherwise (same values). */
+int drsa_amd_avgpool_fwd(const float* a, float* y, int B, int C, int H, int W, int ph, int pw, void* stream);
+
+/* The way back through that block, from the relevance R_y [Bq][C][H/ph][W/pw] at the pool's output (rows
+ * sample * clones + clone) to the dense g [Bq][C][H][W] of the block's conv backward, in one launch.  With
+ * K = float(ph * pw) and pixel p in window (i, j):
+ *   rule 0 (plain gradient of the pool):   t[p] = R_y[i,j] / K
+ *   rule 1 (Epsilon / Norm on the pool):   t[p] = a[p] * ((R_y[i,j] / stab(y[i,j], eps_pool)) / K)
+ *   rel_full[p] = t[p] (when rel_full != NULL: the relevance at the ReLU's output, [Bq][C][H][W])
+ *   g[p] = a[p] > 0 ? (den ? t[p] / stab(den[p], eps_conv) : t[p]) : 0
+ * a [Bq / clones][C][H][W] and y [Bq / clones][C][H/ph][W/pw] are the forward's; y may be NULL under rule 0.
+ * den is the conv rule's denominator at full resolution: [Bq / clones][C][H][W] (den_bcast 0), the shared map
+ * [C][H][W] (den_bcast 1), or NULL (a conv without a rule).  IEEE divisions, no fma.  W % 4 == 0; a, den, g
+ * and rel_full 16-byte aligned (float4 rows); any other argument error: DRSA_EINVAL. */
+int drsa_amd_avgpool_bwd(const float* R_y, const float* y, const float* a, const float* den, int den_bcast, int rule,
+                         float eps_pool, float eps_conv, float* g, float* rel_full, int Bq, int clones, int C, int H,
+                         int W, int ph, int pw, void* stream);
+
 /* Activation vectors and context vectors C = R / (A + 1e-7) at sampled locations
  * (get_vectors_from_maps + compute_context_vectors, preprocessing.py:179-193, 234-256).
  *   act [B, C, H, W]; rel full [B, C, H, W] (rel_amax NULL) or pooled [B, C, H/ph, W/pw] + argmax.
