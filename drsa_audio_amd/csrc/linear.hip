@@ -97,66 +97,12 @@ __global__ __launch_bounds__(256) void linear_kernel(LinArgs a) {
   }
 }
 
-// Forward with K % 4 == 0 (the classifier input, K = 2048): 128-wide K chunks loaded as float4
-// and the next chunk prefetched into registers while the current one runs, so the one
-// k-ordered chain per output (oracle/lrp_exact.c:linear_exact) is no longer bound by one load
-// round trip per 32 k.
-constexpr int LFK = 128;
-
-__global__ __launch_bounds__(256) void linear_fwd_kernel(LinArgs a) {
-  __shared__ __attribute__((aligned(16))) float As[LT][LFK + 4];   // [m][k]
-  __shared__ float Bs[LFK][LT + 1];                               // [k][n]
-  const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
-  const int m0 = blockIdx.x * LT, n0 = blockIdx.y * LT;
-  const int wm = (w & 1) * 16, wn = (w >> 1) * 16;
-  constexpr int NV = LT * LFK / 4 / 256;   // float4 per thread per operand
-  float4 ra[NV], rb[NV];
-#define LFWD_LOAD(K0)                                                                                     \
-  _Pragma("unroll") for (int i = 0; i < NV; ++i) {                                                        \
-    const int idx = tid + i * 256, r = idx / (LFK / 4), k = (K0) + (idx % (LFK / 4)) * 4;                 \
-    const int m = m0 + r, n = n0 + r;                                                                     \
-    const bool oa = m < a.M && k < a.K, ob = n < a.N && k < a.K;                                          \
-    const float4 va = *reinterpret_cast<const float4*>(a.A + (oa ? (size_t)m * a.K + k : 0));             \
-    const float4 vb = *reinterpret_cast<const float4*>(a.W + (ob ? (size_t)n * a.K + k : 0));             \
-    ra[i] = oa ? va : make_float4(0.f, 0.f, 0.f, 0.f);                                                    \
-    rb[i] = ob ? vb : make_float4(0.f, 0.f, 0.f, 0.f);                                                    \
-  }
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  LFWD_LOAD(0)
-  for (int k0 = 0; k0 < a.K; k0 += LFK) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int idx = tid + i * 256, r = idx / (LFK / 4), c = (idx % (LFK / 4)) * 4;
-      *reinterpret_cast<float4*>(&As[r][c]) = ra[i];
-      Bs[c][r] = rb[i].x; Bs[c + 1][r] = rb[i].y; Bs[c + 2][r] = rb[i].z; Bs[c + 3][r] = rb[i].w;
-    }
-    __syncthreads();
-    if (k0 + LFK < a.K) { LFWD_LOAD(k0 + LFK) }
-#pragma unroll
-    for (int kk = 0; kk < LFK; kk += 4) {
-      const float av = As[wm + (lane & 15)][kk + (lane >> 4)];
-      const float bv = Bs[kk + (lane >> 4)][wn + (lane & 15)];
-      acc = mfma16(av, bv, acc);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int m = m0 + wm + (lane >> 4) * 4 + r, n = n0 + wn + (lane & 15);
-    if (m >= a.M || n >= a.N) continue;
-    const size_t o = (size_t)m * a.N + n;
-    const float zz = acc[r] + (a.bias ? a.bias[n] : 0.f);
-    a.out[o] = zz;
-    if (a.out_relu) a.out_relu[o] = zz > 0.f ? zz : (zz != zz ? zz : 0.f);
-  }
-#undef LFWD_LOAD
-}
-
 // Long K (the classifier input, K = 2048) with few output tiles (GTZAN: 512 x 128 = 256 16 x 16
 // tiles): one wave per 16 x 16 output tile, so the grid covers the chip instead of 64 four-wave
 // workgroups; K in 128-wide chunks staged through the wave's own LDS (a wave barrier, no workgroup
 // barrier), the next chunk's 16 float4 loads in flight under the current chunk's 32 MFMAs.  The
-// same single k-ordered chain per output as linear_fwd_kernel (bias added last): the same bits.
+// same single k-ordered chain per output as linear_kernel (bias added last): the same bits.
+// x and W are read as float4: K % 4 == 0 and both 16-byte aligned (drsa_amd_linear_fwd checks).
 constexpr int L1K = 128;
 
 __global__ __launch_bounds__(64) void linear_fwd_w1_kernel(LinArgs a) {
@@ -214,6 +160,8 @@ __global__ __launch_bounds__(64) void linear_fwd_w1_kernel(LinArgs a) {
   }
 }
 
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 }  // namespace
 
 extern "C" {
@@ -221,13 +169,13 @@ extern "C" {
 int drsa_amd_linear_fwd(const float* x, const float* Wt, const float* bias, float* z_out, float* relu_out, int M,
                         int N, int K, void* stream) {
   DRSA_REQUIRE(M > 0 && N > 0 && K > 0, "linear_fwd: bad shape");
+  DRSA_REQUIRE(x && Wt && z_out, "linear_fwd: x, W and z_out are required");
   LinArgs a{};
   a.A = x; a.W = Wt; a.bias = bias; a.out = z_out; a.out_relu = relu_out; a.M = M; a.N = N; a.K = K; a.bwd = 0;
-  // long K (float4-aligned rows): the prefetching kernel; same chain order, same results
-  if (K % 4 == 0 && K >= L1K)
+  // long K with float4-aligned rows (K % 4 == 0, x and W on the 16-byte grid): the prefetching kernel;
+  // anything else takes the scalar loads of linear_kernel.  Same chain order, same results
+  if (K % 4 == 0 && K >= L1K && aligned16(x) && aligned16(Wt))
     hipLaunchKernelGGL(linear_fwd_w1_kernel, dim3((M + 15) / 16, (N + 15) / 16), dim3(64), 0, (hipStream_t)stream, a);
-  else if (K % 4 == 0 && K >= LFK)
-    hipLaunchKernelGGL(linear_fwd_kernel, dim3((M + LT - 1) / LT, (N + LT - 1) / LT), dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(linear_kernel, dim3((M + LT - 1) / LT, (N + LT - 1) / LT), dim3(256), 0, (hipStream_t)stream, a);
   DRSA_LAUNCH_CHECK();
@@ -240,6 +188,10 @@ int drsa_amd_linear_bwd(const float* R, const int* seed_cls, int one_hot, const 
                         float eps_post, float* out, int M, int Nout, int Kin, void* stream) {
   DRSA_REQUIRE(M > 0 && Nout > 0 && Kin > 0, "linear_bwd: bad shape");
   DRSA_REQUIRE(R || seed_cls, "linear_bwd: need R or a seed");
+  DRSA_REQUIRE(z && Wt && out, "linear_bwd: z, W and out are required");
+  DRSA_REQUIRE(xmode == XM_NONE || xmode == XM_MUL, "linear_bwd: xmode must be XM_NONE or XM_MUL");
+  DRSA_REQUIRE(post == POST_NONE || post == POST_DIV || post == POST_MASK,
+               "linear_bwd: post must be POST_NONE, POST_DIV or POST_MASK");
   DRSA_REQUIRE(xmode == XM_NONE || x, "linear_bwd: xmode needs x");
   DRSA_REQUIRE(post == POST_NONE || (x && (den || post == POST_MASK)), "linear_bwd: POST_DIV needs x and den");
   LinArgs a{};

@@ -289,9 +289,15 @@ __global__ __launch_bounds__(256) void rule_bwd_kernel(RuleBwdArgs a) {
   }
 }
 
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// The long-K kernel reads x and every weight set it is given as float4: K % 4 == 0 and all of them on the
+// 16-byte grid (a null Wn is); anything else takes rule_fwd_kernel's scalar loads (the same chains, the
+// same bits).
 template <bool SIGNED, bool NEGDEN>
 void launch_fwd(const RuleFwdArgs& a, hipStream_t s) {
-  if (a.K % 4 == 0 && a.K >= L1K)
+  const bool vec = aligned16(a.x) && aligned16(a.W) && aligned16(a.Wp) && aligned16(a.Wn);
+  if (a.K % 4 == 0 && a.K >= L1K && vec)
     hipLaunchKernelGGL((rule_fwd_w1_kernel<SIGNED, NEGDEN>), dim3((a.M + 15) / 16, (a.N + 15) / 16), dim3(64), 0, s, a);
   else
     hipLaunchKernelGGL((rule_fwd_kernel<SIGNED, NEGDEN>), dim3((a.M + LT - 1) / LT, (a.N + LT - 1) / LT), dim3(256), 0,

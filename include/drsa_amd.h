@@ -345,13 +345,19 @@ int drsa_amd_conv_bwd_den_ring(const float* g, const uint8_t* g_amax, const void
                                const float* den_ring, const float* den_const4, float* out, int Bq, int clones, int cin,
                                int cout, int H, int W, int ng, int xmode, float eps, void* stream);
 
-/* Dense layer forward: z = x W^T + b [, relu(z)]  (classifier Linear layers). */
+/* Dense layer forward: z = x W^T + b [, relu(z)]  (classifier Linear layers).  x [M][K], W [N][K] and
+ * z_out [M][N] are required; a null bias is a layer without one (0 is added), a null relu_out is not
+ * written.  relu(z) keeps a NaN.  Any alignment is accepted: for K % 4 == 0 and K >= 128 the rows are
+ * read as float4 when x and W are 16-byte aligned and element by element otherwise, with the same
+ * k-ascending chain per output and so the same bits. */
 int drsa_amd_linear_fwd(const float* x, const float* W, const float* bias, float* z_out, float* relu_out, int M,
                         int N, int K, void* stream);
 
 /* Dense layer rule backward: g = [z>0?] (R | seed) / stab(z, eps)  ->  out = epi(g W).
  * seed_cls (device int per row) replaces lrp_output_modifier (attribute.py:111-160):
- * R = one_hot ? onehot(cls) : z * onehot(cls). */
+ * R = one_hot ? onehot(cls) : z * onehot(cls).
+ * z, W and out are required, and R or seed_cls.  xmode is XM_NONE or XM_MUL (x required); post is
+ * POST_NONE, POST_DIV (x and den required) or POST_MASK (x required); any other value is refused. */
 int drsa_amd_linear_bwd(const float* R, const int* seed_cls, int one_hot, const float* z, int relu_mask, int rule_eps,
                         float eps, const float* W, const float* x, int xmode, const float* den, int post,
                         float eps_post, float* out, int M, int Nout, int Kin, void* stream);
@@ -365,7 +371,10 @@ int drsa_amd_linear_bwd(const float* R, const int* seed_cls, int one_hot, const 
  *   den_p = f(x+; Wp, bias_p) + f(x-; Wn, 0)
  *   den_n = f(x+; Wn, bias_n) + f(x-; Wp, 0)      (only when den_n is given: Gamma without a ReLU after)
  * every term its own k-ordered chain with its bias added last.  x_signed = 0 declares x >= 0: the x-
- * terms are dropped (exactly zero) and x+ = x.  Wn is required when x_signed or den_n.
+ * terms are dropped (exactly zero) and x+ = x.  Wn is required when x_signed or den_n.  A null bias,
+ * bias_p or bias_n is a layer without that bias: 0 is added to its chain (den_n with a null bias_n is
+ * f(x+; Wn, 0) + f(x-; Wp, 0)).  The long-K (K % 4 == 0, K >= 128) float4 path runs only when x and every
+ * weight set passed are 16-byte aligned; otherwise the element-wise kernel gives the same bits.
  *
  * Backward, one launch: with R = seed | incoming relevance (through the ReLU mask),
  *   g_p = R [z > 0 when zsign] / stab(den_p, eps),  g_n = R [z < 0] / stab(den_n, eps)  (den_n given)

@@ -240,3 +240,37 @@ def test_conv_rejection_table_covers_every_entry_point():
     no table lookup) have their "no kernel" row."""
     assert {e for e, *_ in _CONV_REJECTIONS} == set(_CONV_ORDER)
     assert {e for e, _, c, _ in _CONV_REJECTIONS if c == _U} == set(_CONV_ORDER) - {"conv_fwd_den_ring"}
+
+
+# ---------------------------------------------------------------------------------------------
+# dense head (csrc/linear.hip): one row per argument check, from a valid call (never launched here)
+# ---------------------------------------------------------------------------------------------
+_LIN_ORDER = {
+    "linear_fwd": "x W bias z_out relu_out M N K stream",
+    "linear_bwd": "R seed_cls one_hot z relu_mask rule_eps eps W x xmode den post eps_post out M Nout Kin stream",
+}
+_LIN_VALID = dict({k: 0x10000 * (i + 1) for i, k in enumerate(("x", "W", "bias", "z_out", "relu_out", "R", "z", "den", "out"))},
+                  seed_cls=None, one_hot=0, relu_mask=1, rule_eps=1, eps=1e-6, xmode=_capi.XM_MUL, post=_capi.POST_DIV,
+                  eps_post=1e-6, M=4, N=8, K=16, Nout=8, Kin=16, stream=None)
+_LIN_REJECTIONS = (
+    ("linear_fwd", dict(M=0), "bad shape"),
+    *[("linear_fwd", {k: None}, "x, W and z_out are required") for k in ("x", "W", "z_out")],
+    ("linear_bwd", dict(Kin=0), "bad shape"),
+    ("linear_bwd", dict(R=None), "need R or a seed"),
+    *[("linear_bwd", {k: None}, "z, W and out are required") for k in ("z", "W", "out")],
+    *[("linear_bwd", dict(xmode=v), "xmode must be XM_NONE or XM_MUL") for v in (_capi.XM_SPLIT, -1)],
+    *[("linear_bwd", dict(post=v), "post must be POST_NONE, POST_DIV or POST_MASK") for v in (_capi.POST_DIV_RING, -1)],
+    ("linear_bwd", dict(x=None, post=_capi.POST_NONE), "xmode needs x"),
+    ("linear_bwd", dict(den=None), "POST_DIV needs x and den"),
+    ("linear_bwd", dict(x=None, xmode=_capi.XM_NONE, post=_capi.POST_MASK), "POST_DIV needs x and den"),
+)
+
+
+@pytest.mark.parametrize("entry,changes,needle", _LIN_REJECTIONS,
+                         ids=[f"{e}-{'-'.join(f'{k}={v}' for k, v in c.items())}" for e, c, _ in _LIN_REJECTIONS])
+def test_dense_entry_points_reject_bad_arguments(entry, changes, needle):
+    args = dict(_LIN_VALID, **changes)
+    rc = getattr(_capi.lib(), "drsa_amd_" + entry)(*[args[k] for k in _LIN_ORDER[entry].split()])
+    msg = _capi.lib().drsa_amd_last_error().decode()
+    assert rc == _capi.DRSA_EINVAL, (rc, msg)
+    assert msg.startswith(entry + ":") and needle in msg, msg
