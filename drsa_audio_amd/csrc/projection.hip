@@ -59,15 +59,32 @@ __device__ __forceinline__ void stage_u_padded(float* Us, const float* __restric
   }
 }
 
+// Multi-matrix entries (drsa_amd_projection_*_multi): sample b runs on matrix u_row[b] of a table
+// [n_u][d][d].  The index is uniform in a workgroup (blockIdx.y is the sample): it is read once, as a
+// scalar, clamped into the table, and moves the workgroup's matrix base; everything after it is the
+// single-matrix kernel.  MULTI is a template parameter so that the single-matrix instantiations keep
+// their code and registers (projection_bwd_rc_kernel at d = DP = 64 has 6 VGPRs to spare).
+__device__ __forceinline__ size_t table_offset(const int* __restrict__ u_row, int n_u, int b, int d) {
+  int u = __builtin_amdgcn_readfirstlane(u_row[b]);
+  u = u < 0 ? 0 : u >= n_u ? n_u - 1 : u;
+  return (size_t)u * d * d;
+}
+
 // HOUT = false (the plan's default: projection_bwd recomputes h): only the residual GEMM
 // delta = a P runs and U is not staged -- h = a U is needed by nobody (a' = a + delta).
-template <int DP, bool PAD, bool HOUT>
+template <int DP, bool PAD, bool HOUT, bool MULTI>
 __global__ __launch_bounds__(256) void projection_fwd_kernel(const float* __restrict__ a, const float* __restrict__ U,
                                                             const float* __restrict__ Pm,
                                                             float* __restrict__ h, float* __restrict__ ap,
                                                             float* __restrict__ pooled, uint8_t* __restrict__ amax,
-                                                            int d_in, int H, int W, int pool) {
+                                                            int d_in, int H, int W, int pool,
+                                                            const int* __restrict__ u_row, int n_u) {
   const int d = PAD ? d_in : DP;   // PAD = false: d == DP at compile time (no padding code)
+  if constexpr (MULTI) {
+    const size_t uo = table_offset(u_row, n_u, blockIdx.y, d);
+    U += uo;
+    Pm += uo;
+  }
   constexpr int P = 64, LD = DP + 1, PL = P + 4;
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* Us = sm;               // [DP][LD]   U[c][j] (HOUT only)
@@ -211,13 +228,14 @@ __global__ __launch_bounds__(256) void projection_fwd_kernel(const float* __rest
 // ===========================================================================
 constexpr int PT_BWD = 1;   // tiles per workgroup (stored-h backward)
 
-template <int DP, bool PAD>
+template <int DP, bool PAD, bool MULTI>
 __global__ __launch_bounds__(256) void projection_bwd_kernel(
     const float* __restrict__ gp, const uint8_t* __restrict__ amax, const float* __restrict__ ap,
     const float* __restrict__ h, const float* __restrict__ a, const float* __restrict__ den,
     const float* __restrict__ U, float* __restrict__ G, int d_in, int H, int W, int K, float eps_proj, float eps_den,
-    int sparse, int has_den, int fanout) {
+    int sparse, int has_den, int fanout, const int* __restrict__ u_row, int n_u) {
   const int d = PAD ? d_in : DP;
+  if constexpr (MULTI) U += table_offset(u_row, n_u, blockIdx.y, d);
   constexpr int P = 64, LD = DP + 1, PL = P + 4;
   constexpr int NB = DP / 16, TILES = NB * (P / 16), QW = TILES / 4;   // 16x16 blocks; per wave
   // Per wave: pixel block pb = wave, channel blocks cb = 0..NB-1 (q = wave + 4 i).  Its h, a,
@@ -357,12 +375,18 @@ constexpr int PT_RC = 2;
 // SPARSE (a 2x2 max-pool follows the projection: gp is pooled, amax selects) and DEN (the lower
 // layer's denominator is given) are compile-time: tested per element at run time they cost the
 // DP = 64 kernel 48 of its 71 branches.
-template <int DP, bool PAD, bool SPARSE, bool DEN>
+template <int DP, bool PAD, bool SPARSE, bool DEN, bool MULTI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DP <= 64 ? 3 : 1))) void projection_bwd_rc_kernel(
     const float* __restrict__ gp, const uint8_t* __restrict__ amax, const float* __restrict__ a,
     const float* __restrict__ den, const float* __restrict__ U, const float* __restrict__ Pm, float* __restrict__ G,
-    int d_in, int H, int W, int K, float eps_proj, float eps_den, int fanout) {
+    int d_in, int H, int W, int K, float eps_proj, float eps_den, int fanout, const int* __restrict__ u_row,
+    int n_u) {
   const int d = PAD ? d_in : DP;
+  if constexpr (MULTI) {
+    const size_t uo = table_offset(u_row, n_u, blockIdx.y, d);
+    U += uo;
+    Pm += uo;
+  }
   constexpr int P = 64, LD = DP + 1, PW = 16, NB = DP / 16;
   constexpr bool PF = DP <= 64;   // keep a / den of the output rows in registers
   // the tile's relevance gather (gp, and amax when SPARSE) as one batch of loads in flight across
@@ -615,6 +639,73 @@ size_t proj_bwd_lds() { return ((size_t)D * (D + 1) + 2 * (size_t)D * 68) * size
 template <int D>
 size_t proj_bwd_rc_lds() { return ((size_t)D * (D + 1) + 4 * 2 * (size_t)D * 16) * sizeof(float); }
 
+// The single-matrix and the multi-matrix entries share their checks and their dispatch: u_row == nullptr is the
+// single-matrix form (U, P one matrix each), otherwise U and P are tables [n_u][D][D] and u_row [B] names each
+// row's matrix.  ``who`` prefixes every message.
+int projection_fwd_impl(const char* who, const float* a, const float* U, const float* P, const int* u_row, int n_u,
+                        float* h, float* ap, float* pooled, uint8_t* amax, int B, int D, int H, int W, int pool,
+                        void* stream) {
+  const int TW = W < 32 ? W : 32;
+  DRSA_REQUIRE((W == 8 || W == 16 || W % 32 == 0) && H % (64 / TW) == 0,
+               "%s: W must be 8, 16 or a multiple of 32 and H a multiple of 64/min(W,32) (got %dx%d)", who, H, W);
+  DRSA_REQUIRE(!pool || (pooled && amax), "%s: pool needs outputs", who);
+  DRSA_REQUIRE((int64_t)D * H * W < ((int64_t)1 << 31), "%s: one sample's d x H x W must stay below 2^31", who);
+  DRSA_REQUIRE(pool || ap, "%s: without pool a' (ap) is the output", who);
+  hipStream_t s = (hipStream_t)stream;
+  const int tiles = (H / (64 / TW)) * (W / TW);
+  const dim3 grid((tiles + PT - 1) / PT, B);
+  return with_proj_dp(D, who, [&](auto dp) -> int {
+    constexpr int DP = decltype(dp)::value;
+    return with_flag(D != DP, [&](auto pad) -> int {
+      return with_flag(h != nullptr, [&](auto hout) -> int {
+        return with_flag(u_row != nullptr, [&](auto multi) -> int {
+          return launch_proj(
+              projection_fwd_kernel<DP, decltype(pad)::value, decltype(hout)::value, decltype(multi)::value>, grid,
+              proj_fwd_lds<DP>(h != nullptr), s, a, U, P, h, ap, pooled, amax, D, H, W, pool, u_row, n_u);
+        });
+      });
+    });
+  });
+}
+
+int projection_bwd_impl(const char* who, const float* gp, const uint8_t* amax, const float* ap, const float* h,
+                        const float* a, const float* den, const float* U, const float* P, const int* u_row, int n_u,
+                        float* G, int B, int D, int H, int W, int K, float eps_proj, float eps_den, int fanout,
+                        void* stream) {
+  const int TW = W < 32 ? W : 32;
+  DRSA_REQUIRE(fanout >= 0 && fanout <= 2, "%s: fanout must be 0, 1 or 2", who);
+  DRSA_REQUIRE((int64_t)D * H * W < ((int64_t)1 << 31), "%s: one sample's d x H x W must stay below 2^31", who);
+  DRSA_REQUIRE(gp && a && U && G && ((ap && h) || P),
+               "%s: gp, a, U, G and P (when h / a' are recomputed) are required", who);
+  DRSA_REQUIRE((W == 8 || W == 16 || W % 32 == 0) && H % (64 / TW) == 0,
+               "%s: W must be 8, 16 or a multiple of 32 and H a multiple of 64/min(W,32) (got %dx%d)", who, H, W);
+  DRSA_REQUIRE(K > 0 && D % K == 0, "%s: K must divide d", who);
+  hipStream_t s = (hipStream_t)stream;
+  const int tiles = (H / (64 / TW)) * (W / TW);
+  const int sparse = amax != nullptr, has_den = den != nullptr;
+  const bool recompute = !ap || !h;   // h and a' rebuilt from a
+  return with_proj_dp(D, who, [&](auto dp) -> int {
+    constexpr int DP = decltype(dp)::value;
+    return with_flag(D != DP, [&](auto pad) -> int {
+      constexpr bool PAD = decltype(pad)::value;
+      return with_flag(u_row != nullptr, [&](auto multi) -> int {
+        constexpr bool MULTI = decltype(multi)::value;
+        if (recompute)
+          return with_flag(sparse, [&](auto sp) -> int {
+            return with_flag(has_den, [&](auto dn) -> int {
+              return launch_proj(projection_bwd_rc_kernel<DP, PAD, decltype(sp)::value, decltype(dn)::value, MULTI>,
+                                 dim3((tiles + PT_RC - 1) / PT_RC, B), proj_bwd_rc_lds<DP>(), s, gp, amax, a, den, U, P,
+                                 G, D, H, W, K, eps_proj, eps_den, fanout, u_row, n_u);
+            });
+          });
+        return launch_proj(projection_bwd_kernel<DP, PAD, MULTI>, dim3((tiles + PT_BWD - 1) / PT_BWD, B),
+                           proj_bwd_lds<DP>(), s, gp, amax, ap, h, a, den, U, G, D, H, W, K, eps_proj, eps_den, sparse,
+                           has_den, fanout, u_row, n_u);
+      });
+    });
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -628,58 +719,39 @@ int drsa_amd_projection_residual(const float* U, int D, float* P, void* stream) 
 
 int drsa_amd_projection_fwd(const float* a, const float* U, const float* P, float* h, float* ap, float* pooled,
                             uint8_t* amax, int B, int D, int H, int W, int pool, void* stream) {
-  const int TW = W < 32 ? W : 32;
   DRSA_REQUIRE(a && U && P, "projection_fwd: a, U and P (drsa_amd_projection_residual) are required");
-  DRSA_REQUIRE((W == 8 || W == 16 || W % 32 == 0) && H % (64 / TW) == 0,
-               "projection_fwd: W must be 8, 16 or a multiple of 32 and H a multiple of 64/min(W,32) (got %dx%d)", H, W);
-  DRSA_REQUIRE(!pool || (pooled && amax), "projection_fwd: pool needs outputs");
-  DRSA_REQUIRE((int64_t)D * H * W < ((int64_t)1 << 31), "projection_fwd: one sample's d x H x W must stay below 2^31");
-  DRSA_REQUIRE(pool || ap, "projection_fwd: without pool a' (ap) is the output");
-  hipStream_t s = (hipStream_t)stream;
-  const int tiles = (H / (64 / TW)) * (W / TW);
-  const dim3 grid((tiles + PT - 1) / PT, B);
-  return with_proj_dp(D, "projection_fwd", [&](auto dp) -> int {
-    constexpr int DP = decltype(dp)::value;
-    return with_flag(D != DP, [&](auto pad) -> int {
-      return with_flag(h != nullptr, [&](auto hout) -> int {
-        return launch_proj(projection_fwd_kernel<DP, decltype(pad)::value, decltype(hout)::value>, grid,
-                           proj_fwd_lds<DP>(h != nullptr), s, a, U, P, h, ap, pooled, amax, D, H, W, pool);
-      });
-    });
-  });
+  return projection_fwd_impl("projection_fwd", a, U, P, nullptr, 0, h, ap, pooled, amax, B, D, H, W, pool, stream);
 }
 
 int drsa_amd_projection_bwd(const float* gp, const uint8_t* amax, const float* ap, const float* h, const float* a,
                             const float* den, const float* U, const float* P, float* G, int B, int D, int H, int W,
                             int K, float eps_proj, float eps_den, int fanout, void* stream) {
-  const int TW = W < 32 ? W : 32;
-  DRSA_REQUIRE(fanout >= 0 && fanout <= 2, "projection_bwd: fanout must be 0, 1 or 2");
-  DRSA_REQUIRE((int64_t)D * H * W < ((int64_t)1 << 31), "projection_bwd: one sample's d x H x W must stay below 2^31");
-  DRSA_REQUIRE(gp && a && U && G && ((ap && h) || P),
-               "projection_bwd: gp, a, U, G and P (when h / a' are recomputed) are required");
-  DRSA_REQUIRE((W == 8 || W == 16 || W % 32 == 0) && H % (64 / TW) == 0,
-               "projection_bwd: W must be 8, 16 or a multiple of 32 and H a multiple of 64/min(W,32) (got %dx%d)", H, W);
-  DRSA_REQUIRE(K > 0 && D % K == 0, "projection_bwd: K must divide d");
-  hipStream_t s = (hipStream_t)stream;
-  const int tiles = (H / (64 / TW)) * (W / TW);
-  const int sparse = amax != nullptr, has_den = den != nullptr;
-  const bool recompute = !ap || !h;   // h and a' rebuilt from a
-  return with_proj_dp(D, "projection_bwd", [&](auto dp) -> int {
-    constexpr int DP = decltype(dp)::value;
-    return with_flag(D != DP, [&](auto pad) -> int {
-      constexpr bool PAD = decltype(pad)::value;
-      if (recompute)
-        return with_flag(sparse, [&](auto sp) -> int {
-          return with_flag(has_den, [&](auto dn) -> int {
-            return launch_proj(projection_bwd_rc_kernel<DP, PAD, decltype(sp)::value, decltype(dn)::value>,
-                               dim3((tiles + PT_RC - 1) / PT_RC, B), proj_bwd_rc_lds<DP>(), s, gp, amax, a, den, U, P,
-                               G, D, H, W, K, eps_proj, eps_den, fanout);
-          });
-        });
-      return launch_proj(projection_bwd_kernel<DP, PAD>, dim3((tiles + PT_BWD - 1) / PT_BWD, B), proj_bwd_lds<DP>(), s,
-                         gp, amax, ap, h, a, den, U, G, D, H, W, K, eps_proj, eps_den, sparse, has_den, fanout);
-    });
-  });
+  return projection_bwd_impl("projection_bwd", gp, amax, ap, h, a, den, U, P, nullptr, 0, G, B, D, H, W, K, eps_proj,
+                             eps_den, fanout, stream);
+}
+
+int drsa_amd_projection_fwd_multi(const float* a, const float* U_tab, const float* P_tab, const int* u_row, int n_u,
+                                  float* h, float* ap, float* pooled, uint8_t* amax, int B, int D, int H, int W,
+                                  int pool, void* stream) {
+  const char* who = "projection_fwd_multi";
+  DRSA_REQUIRE(a && U_tab && P_tab && u_row,
+               "%s: a, U_tab, P_tab (drsa_amd_projection_residual per matrix) and u_row are required", who);
+  DRSA_REQUIRE(n_u >= 1, "%s: the table needs at least one matrix (n_u=%d)", who, n_u);
+  DRSA_REQUIRE(D >= 1 && D <= 128, "%s: need 1 <= d <= 128 (got %d)", who, D);
+  return projection_fwd_impl(who, a, U_tab, P_tab, u_row, n_u, h, ap, pooled, amax, B, D, H, W, pool, stream);
+}
+
+int drsa_amd_projection_bwd_multi(const float* gp, const uint8_t* amax, const float* ap, const float* h,
+                                  const float* a, const float* den, const float* U_tab, const float* P_tab,
+                                  const int* u_row, int n_u, float* G, int B, int D, int H, int W, int K,
+                                  float eps_proj, float eps_den, int fanout, void* stream) {
+  const char* who = "projection_bwd_multi";
+  DRSA_REQUIRE(U_tab && P_tab && u_row, "%s: U_tab, P_tab and u_row are required", who);
+  DRSA_REQUIRE(n_u >= 1, "%s: the table needs at least one matrix (n_u=%d)", who, n_u);
+  DRSA_REQUIRE(D >= 1 && D <= 128, "%s: need 1 <= d <= 128 (got %d)", who, D);
+  return projection_bwd_impl(who, gp, amax, ap, h, a, den, U_tab, P_tab, u_row, n_u, G, B, D, H, W, K, eps_proj, eps_den,
+                             fanout, stream);
 }
 
 }  // extern "C"
+

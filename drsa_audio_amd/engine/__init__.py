@@ -36,14 +36,20 @@ def _fingerprint(model):
     """Parameters AND buffers: the plan folds BatchNorm running statistics into the weights, so a
     train-mode forward or a buffers-only load_state_dict must recompile.  Also the DRSA projection
     matrices, which are plain tensor attributes (``Projection.U``, ``InvProjection.U_inv``,
-    ``ProjectionModel.U``; cxai/model/modify_model.py:4-123): the plan caches U and P = UU^T - I, so
-    an in-place update (``_version``) or a rebinding (``data_ptr``) of U must recompile too."""
+    ``ProjectionModel.U``; cxai/model/modify_model.py:4-123) and the table of a MultiProjectionModel
+    (``U_tab``): the plan caches U and P = UU^T - I, so an in-place update (``_version``) or a
+    rebinding (``data_ptr``) of U, or of any entry of the table, must recompile too."""
     proj = []
     for m in model.modules():
         for attr in ("U", "U_inv"):
             t = getattr(m, attr, None)
             if isinstance(t, torch.Tensor):
                 proj.append((attr, t.data_ptr(), t._version))
+        # a plain attribute of the Multi* modules: read from the instance dict, since a getattr that misses costs
+        # every other module of every model a walk through nn.Module.__getattr__ on each get_engine call
+        t = m.__dict__.get("U_tab")
+        if isinstance(t, torch.Tensor):
+            proj.append(("U_tab", t.data_ptr(), t._version))
     return (tuple((p.data_ptr(), p._version) for p in model.parameters()) +
             tuple((b.data_ptr(), b._version) for b in model.buffers()) + tuple(proj))
 

@@ -45,6 +45,18 @@ class ProjGroup:
     eps_proj: float
     mask: bool          # SubspaceHook on the filter
     pool_after: bool
+    # MultiProjectionModel: a table [n][d][d] of matrices (U is None), the residuals likewise; the row -> matrix
+    # index is per-call data (LRPEngine.forward(u_rows=...)), never part of the plan
+    U_tab: Optional[torch.Tensor] = None
+    P_tab: Optional[torch.Tensor] = None
+
+    @property
+    def multi(self) -> bool:
+        return self.U_tab is not None
+
+    @property
+    def d(self) -> int:
+        return int((self.U_tab if self.multi else self.U).size(-1))
 
 
 @dataclass
@@ -293,8 +305,10 @@ def parse(model: nn.Module, composite, bf16: bool = False) -> Tuple[List[ConvSta
         _rule_ok_on_activation(rules.get(relu_name))
         j += 1
         proj = None
-        if j < n and _is(feats[j][1], "Projection"):
-            if not (j + 2 < n and _is(feats[j + 1][1], "SubspaceFilter") and _is(feats[j + 2][1], "InvProjection")):
+        if j < n and (_is(feats[j][1], "Projection") or _is(feats[j][1], "MultiProjection")):
+            multi = _is(feats[j][1], "MultiProjection")
+            if not (j + 2 < n and _is(feats[j + 1][1], "SubspaceFilter")
+                    and _is(feats[j + 2][1], "MultiInvProjection" if multi else "InvProjection")):
                 raise EngineError("engine: Projection must be followed by SubspaceFilter, InvProjection")
             pm = feats[j][1]
             r_p, r_f, r_i = (rules.get(f"features.{feats[j + d][0]}") for d in range(3))
@@ -302,8 +316,11 @@ def parse(model: nn.Module, composite, bf16: bool = False) -> Tuple[List[ConvSta
                 raise EngineError("engine: projection layers need Epsilon rules (get_class_composite)")
             if r_f is not None and type(r_f).__name__ != "SubspaceHook":
                 raise EngineError("engine: only SubspaceHook is supported on the subspace filter")
-            proj = ProjGroup(U=_host(pm.U).contiguous(), K=int(pm.num_concepts), P=None, eps_inv=_eps_of(r_i),
-                             eps_proj=_eps_of(r_p), mask=r_f is not None, pool_after=False)
+            if multi and feats[j + 2][1].U_tab is not pm.U_tab:
+                raise EngineError("engine: MultiProjection and MultiInvProjection must share one table of matrices")
+            proj = ProjGroup(U=None if multi else _host(pm.U).contiguous(), K=int(pm.num_concepts), P=None,
+                             eps_inv=_eps_of(r_i), eps_proj=_eps_of(r_p), mask=r_f is not None, pool_after=False,
+                             U_tab=_host(pm.U_tab).contiguous() if multi else None)
             if r_f is not None and int(r_f.num_concepts) != proj.K:
                 raise EngineError("engine: SubspaceHook num_concepts differs from the projection")
             j += 3

@@ -17,7 +17,9 @@ Forward: one ``drsa_amd_conv_fwd`` per conv stage computes y = pool(relu(conv)),
 denominator at the argmax (the only place relevance arrives).  Backward: one ``drsa_amd_conv_bwd`` per conv stage,
 the max-pool/ReLU backward folded into its input, the next lower layer's division folded into its output.  The
 subspace path fans one forward out into K+1 relevance clones at the projection (``drsa_amd_projection_bwd``),
-instead of replicating the batch K+1 times (explainer.py:92).  A dense stage under Epsilon (or no rule) is one
+instead of replicating the batch K+1 times (explainer.py:92).  A MultiProjectionModel's plan holds a table of
+projection matrices and runs ``drsa_amd_projection_fwd_multi`` / ``_bwd_multi`` on the per-call ``u_rows`` (the table
+index of each row: mixed-class batches in one pass).  A dense stage under Epsilon (or no rule) is one
 ``drsa_amd_linear_fwd`` and one ``drsa_amd_linear_bwd``; under Gamma / ZPlus its forward also writes the rule's
 denominators (``drsa_amd_linear_rule_fwd``) and under Gamma / ZPlus / WSquare / Flat its backward is one
 ``drsa_amd_linear_rule_bwd`` with a chain per term of R_in (pf.py:18-27, 257-292: the dense rule comes from the
@@ -204,12 +206,18 @@ class LRPEngine:
             st.wts_bwd_bf = _bf16_layout(st.wts_bwd, cout_p, cin_o)
         if st.proj is not None:
             P = st.proj
-            if P.U.size(0) != st.cout:
+            if P.d != st.cout:
                 raise EngineError("engine: projection width differs from the conv channels")
-            P.U = P.U.to(dev).contiguous()
-            P.P = torch.empty_like(P.U)
-            _capi.call("drsa_amd_projection_residual", P.U.data_ptr(), P.U.size(0), P.P.data_ptr(),
-                       _capi.stream_ptr(dev))
+            if P.multi:     # the table and, per matrix, its residual
+                P.U_tab = P.U_tab.to(dev).contiguous()
+                P.P_tab = torch.empty_like(P.U_tab)
+                for U, Pm in zip(P.U_tab, P.P_tab):
+                    _capi.call("drsa_amd_projection_residual", U.data_ptr(), P.d, Pm.data_ptr(), _capi.stream_ptr(dev))
+            else:
+                P.U = P.U.to(dev).contiguous()
+                P.P = torch.empty_like(P.U)
+                _capi.call("drsa_amd_projection_residual", P.U.data_ptr(), P.U.size(0), P.P.data_ptr(),
+                           _capi.stream_ptr(dev))
 
     def _prepare_dense(self, ds: DenseStage):   # the weights and the rule's sets (formed on the host) to the device
         dev = self.device
@@ -282,6 +290,46 @@ class LRPEngine:
         p[:, :, :t.size(2), :t.size(3)].copy_(t)
         return p
 
+    # ------------------------------------------------------- matrix per row
+    def _multi_proj(self):
+        """The plan's multi-matrix projection group (MultiProjectionModel), or None (looked up once)."""
+        try:
+            return self._multi
+        except AttributeError:
+            self._multi = next((st.proj for st in self.stages if st.proj is not None and st.proj.multi), None)
+            return self._multi
+
+    def _u_rows(self, u_rows, B: int) -> Optional[torch.Tensor]:
+        """``u_rows`` (a host sequence or an int tensor [B]: the table index of each row) checked on the host and
+        uploaded as the int32 [B] the ``_multi`` kernels read; None for a single-matrix plan.  Per-call data: no
+        part of the schedule or of the plan."""
+        P = self._multi_proj()
+        if P is None:
+            if u_rows is not None:
+                raise ValueError("u_rows given to a single-matrix plan (ProjectionModel): it has one U for every row; "
+                                 "per-row matrices need a MultiProjectionModel")
+            return None
+        if u_rows is None:
+            raise ValueError("this plan has a matrix per row (MultiProjectionModel): pass u_rows, one table index "
+                             "per row")
+        if isinstance(u_rows, torch.Tensor):
+            if u_rows.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+                raise ValueError(f"u_rows must be an integer tensor (got {u_rows.dtype})")
+            host = u_rows.detach().reshape(-1).to("cpu", torch.int64)
+        else:
+            try:
+                host = torch.tensor([int(v) for v in u_rows], dtype=torch.int64)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"u_rows must be a sequence of table indices or an int tensor [B] ({e})") from None
+        if host.numel() != B:
+            raise ValueError(f"u_rows has {host.numel()} entries for a batch of {B} rows")
+        n_u = P.U_tab.size(0)
+        bad = ((host < 0) | (host >= n_u)).nonzero()
+        if bad.numel():
+            r = int(bad[0])
+            raise ValueError(f"u_rows[{r}] = {int(host[r])} is outside the table of {n_u} matrices (row {r})")
+        return host.to(torch.int32).to(self.device)
+
     # ---------------------------------------------------------------- forward
     def _conv_fwd(self, tag, name, st: ConvStage, neg: bool, cur, den_map, out, amax, den, B, h, w, ng, pool, s):
         """One conv forward launch of entry point ``name`` on its weight layout (fp32 or bf16)."""
@@ -298,11 +346,13 @@ class LRPEngine:
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor, capture: Union[None, int, Tuple[int, ...]] = None,
-                taps: Tuple[int, ...] = ()) -> torch.Tensor:
+                taps: Tuple[int, ...] = (), u_rows=None) -> torch.Tensor:
         """Model forward with all LRP state (argmax, denominators) kept on device.  ``capture``:
         index of a conv stage, or a tuple of them, whose full-resolution ReLU output is kept even though a
         max-pool follows (the reference's store_hook, preprocessing.py:92-103).  ``taps``: the taps the
-        backward will be given (a tapped stage leaves its denominator as a per-sample copy)."""
+        backward will be given (a tapped stage leaves its denominator as a per-sample copy).  ``u_rows``: for a
+        MultiProjectionModel plan, the table index of each row's projection matrix (a host sequence or an int
+        tensor [B]; checked on the host); the backward of this forward uses the same."""
         _capi.require_gpu(x, "input", dtype=None)
         x = x.detach()
         if self.bf16:
@@ -311,11 +361,13 @@ class LRPEngine:
         if x.dim() != 4 or x.size(1) != self.stages[0].cin:
             raise ValueError(f"input must be [B, {self.stages[0].cin}, H, W]")
         B, _, H, W = x.shape
+        u_dev = self._u_rows(u_rows, B)
         capture, taps = tuple(capture) if isinstance(capture, (tuple, list)) else capture, tuple(taps)
         conv_steps, dense_steps = self._schedule(B, H, W, capture, None, 0, taps=taps)
         self._cur_bufs = self._buffers.setdefault(("fwd", B, H, W), {})
         s = _capi.stream_ptr(self.device)
-        state = {"B": B, "stages": [], "key": (B, H, W, capture), "taps": taps, "tap_rel": {}, "avg_rel": {}}
+        state = {"B": B, "stages": [], "key": (B, H, W, capture), "taps": taps, "tap_rel": {}, "avg_rel": {},
+                 "u_rows": u_dev}
         cur = x
         for li, (st, sp) in enumerate(zip(self.stages, conv_steps)):
             (h, w), (ho, wo), C = sp.hw, sp.out_hw, st.cout
@@ -384,9 +436,14 @@ class LRPEngine:
                 if P.pool_after:
                     pooled = self._buf((li, "y_pad" if padded else "y"), (B, C, hk // 2, wk // 2))
                     amax = self._buf((li, "amax"), (B, C, hk // 2, wk // 2), torch.uint8)
-                self._call("projection_fwd", "drsa_amd_projection_fwd", ak.data_ptr(), P.U.data_ptr(), P.P.data_ptr(),
-                           _capi.ptr(hb), _capi.ptr(ap), _capi.ptr(pooled), _capi.ptr(amax), B, C, hk, wk,
-                           1 if P.pool_after else 0, s)
+                if P.multi:
+                    self._call("projection_fwd", "drsa_amd_projection_fwd_multi", ak.data_ptr(), P.U_tab.data_ptr(),
+                               P.P_tab.data_ptr(), u_dev.data_ptr(), P.U_tab.size(0), _capi.ptr(hb), _capi.ptr(ap),
+                               _capi.ptr(pooled), _capi.ptr(amax), B, C, hk, wk, 1 if P.pool_after else 0, s)
+                else:
+                    self._call("projection_fwd", "drsa_amd_projection_fwd", ak.data_ptr(), P.U.data_ptr(),
+                               P.P.data_ptr(), _capi.ptr(hb), _capi.ptr(ap), _capi.ptr(pooled), _capi.ptr(amax), B, C,
+                               hk, wk, 1 if P.pool_after else 0, s)
                 y = pooled if P.pool_after else ap
                 if padded:
                     y = self._buf((li, "y" if P.pool_after else "ap_crop"), (B, C, ho, wo))
@@ -471,20 +528,23 @@ class LRPEngine:
     @torch.no_grad()
     def backward(self, seed: Optional[torch.Tensor] = None, cls: Optional[torch.Tensor] = None,
                  one_hot: bool = False, fanout: int = 0, stop_after: Optional[int] = None,
-                 taps: Tuple[int, ...] = ()) -> torch.Tensor:
+                 taps: Tuple[int, ...] = (), u_rows=None) -> torch.Tensor:
         """Relevance at the input.  ``seed`` [B, n_out] (output relevance) or ``cls`` [B] int32 (lrp_output_modifier
         semantics).  ``fanout``: the projection stage emits K+1 clones per sample (HeatmapGenerator path); otherwise
         rows are treated as the reference's replicated batch.  ``stop_after``: stop once the relevance at the OUTPUT
         of conv stage ``stop_after`` is known and return it (pool resolution when that stage pools).  ``taps``: conv
         stages above ``stop_after`` (ascending; the forward was given the same) whose output relevance is recorded
         on the way down, ``self.last["tap_rel"][stage]``: the buffer the launch above wrote without its post step,
-        readable until the next call; drsa_amd_relevance_post then makes the g the walk goes on with."""
+        readable until the next call; drsa_amd_relevance_post then makes the g the walk goes on with.  ``u_rows``
+        (MultiProjectionModel plans): default, the forward's; given, checked like the forward's and used instead
+        (with ``fanout`` 0 one index per replicated row, as the forward saw them)."""
         st0 = self.last
         if st0 is None:
             raise RuntimeError("backward() before forward()")
         B, taps = st0["B"], tuple(taps)
         if taps != st0["taps"]:
             raise ValueError(f"backward(taps={taps}) after forward(taps={st0['taps']}): they must be the same")
+        u_dev = st0["u_rows"] if u_rows is None else self._u_rows(u_rows, B)
         conv_steps, dense_steps = self._schedule(*st0["key"], stop_after, fanout, taps=taps)
         s = _capi.stream_ptr(self.device)
         self._cur_bufs = self._buffers.setdefault(("bwd", B, fanout), {})
@@ -550,11 +610,16 @@ class LRPEngine:
                     gk = self._pad_map((li, "g_pad"), g, *((hk // 2, wk // 2) if P.pool_after else (hk, wk)))
                     denk = None if denk is None else self._pad_map((li, "den_pad"), denk, hk, wk)
                     Gk = self._buf((li, "G_pad"), (Bq, st.cout, hk, wk))
-                self._call("projection_bwd", "drsa_amd_projection_bwd", gk.data_ptr(),
-                           _capi.ptr(rec["amax"] if P.pool_after else None), _capi.ptr(rec["ap"] if store else None),
-                           _capi.ptr(rec["h"]), rec["a_k"].data_ptr(), _capi.ptr(denk), P.U.data_ptr(), P.P.data_ptr(),
-                           Gk.data_ptr(), B, st.cout, hk, wk, P.K, P.eps_inv, st.eps if denk is not None else 0.0,
-                           int(fanout), s)
+                head = (gk.data_ptr(), _capi.ptr(rec["amax"] if P.pool_after else None),
+                        _capi.ptr(rec["ap"] if store else None), _capi.ptr(rec["h"]), rec["a_k"].data_ptr(),
+                        _capi.ptr(denk))
+                tail = (Gk.data_ptr(), B, st.cout, hk, wk, P.K, P.eps_inv, st.eps if denk is not None else 0.0,
+                        int(fanout), s)
+                if P.multi:
+                    self._call("projection_bwd", "drsa_amd_projection_bwd_multi", *head, P.U_tab.data_ptr(),
+                               P.P_tab.data_ptr(), u_dev.data_ptr(), P.U_tab.size(0), *tail)
+                else:
+                    self._call("projection_bwd", "drsa_amd_projection_bwd", *head, P.U.data_ptr(), P.P.data_ptr(), *tail)
                 if rec["pad"]:
                     G.copy_(Gk[:, :, :h, :w])
                 g = G
@@ -654,19 +719,20 @@ class LRPEngine:
     # -------------------------------------------------------------- heatmaps
     @torch.no_grad()
     def subspace_heatmaps(self, x: torch.Tensor, class_idx=None, cls: Optional[torch.Tensor] = None,
-                          one_hot: bool = False, standard: str = "sum") -> dict:
+                          one_hot: bool = False, standard: str = "sum", u_rows=None) -> dict:
         """HeatmapGenerator.generate_subspace_heatmaps on device: one shared forward, the top backward once,
         relevance clones below the projection, then split/sum/sort.  ``standard="sum"``: K clones, the standard
         heatmap is the sum of the K concept heatmaps (every rule is linear in the relevance, so this is clone 0 up to
         fp32 rounding; the bottom of the network runs K instead of K+1 times).  ``"clone"``: K+1 clones, the standard
-        heatmap is clone 0 as in the reference's replicated batch (explainer.py:92)."""
+        heatmap is clone 0 as in the reference's replicated batch (explainer.py:92).  ``u_rows``: the table index of
+        each row's matrix, for a MultiProjectionModel plan (required there, refused elsewhere)."""
         if standard not in ("sum", "clone"):
             raise ValueError("standard must be 'sum' or 'clone'")
         proj = [st.proj for st in self.stages if st.proj is not None]
         if len(proj) != 1 or not proj[0].mask:
             raise EngineError("subspace heatmaps need exactly one projection group with a SubspaceHook")
         K = proj[0].K
-        self.forward(x)
+        self.forward(x, u_rows=u_rows)
         B = x.size(0)
         if cls is None:
             cls = torch.full((B,), int(class_idx), dtype=torch.int32, device=self.device)

@@ -1,6 +1,7 @@
 """Concept (subspace) heatmaps, drop-in for ``cxai.xai.explain.explainer``.
 
 * ``HeatmapGenerator``            — reference explainer.py:15-176
+* ``MultiHeatmapGenerator``       — (no reference) a mixed-class batch in one pass: a projection matrix per row
 * ``get_class_composite``         — reference explainer.py:179-203
 * ``compute_subspace_relevances`` — reference explainer.py:206-242
 
@@ -13,7 +14,7 @@ given the shared forward).  ``info`` holds numpy arrays exactly like the referen
 """
 from __future__ import annotations
 
-from typing import List, Tuple
+from typing import List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -21,7 +22,7 @@ import torch.nn as nn
 
 from ... import _capi
 from ...engine import get_engine
-from ...model.modify_model import ProjectionModel
+from ...model.modify_model import MultiProjectionModel, ProjectionModel
 from ...utils.constants import CLASS_IDX_MAPPER, CLASS_IDX_MAPPER_TOY
 from ...zennit.composites import Composite, NameMapComposite
 from ...zennit.rules import Epsilon
@@ -141,6 +142,83 @@ class HeatmapGenerator:
         mask = np.argsort(rel, axis=-1)[..., ::-1]
         ar = np.arange(b)[:, None]
         return subspace_heatmaps[ar, mask], rel[ar, mask], mask
+
+
+class MultiHeatmapGenerator:
+    """HeatmapGenerator for a batch of mixed classes: ``Us`` maps class names to their DRSA matrices, and every row
+    names the class that is attributed (``sample_classes``) and the class whose matrix it goes through
+    (``subspace_classes``, default the same).  One MultiProjectionModel, one composite and so one engine plan serve
+    every class mix; the per-row choices are data of the call.  Row i of every result is, bit for bit, what
+    ``HeatmapGenerator(model, Us[subspace_classes[i]], name_map, sample_classes[i], ...)`` gives for that row."""
+
+    def __init__(self, model: nn.Module, Us: Mapping[str, torch.Tensor], name_map: List[Tuple[List[str], object]],
+                 num_concepts: int = 4, layer_idx: int = 10, device: str | torch.device = torch.device("cuda"),
+                 canonizers=None, standard: str = "clone", case: Optional[str] = None) -> None:
+        if standard not in ("sum", "clone"):
+            raise ValueError("standard must be 'sum' or 'clone'")
+        if not isinstance(Us, Mapping) or not Us:
+            raise ValueError("Us must be a non-empty mapping of class names to projection matrices")
+        self.standard = standard
+        self.device = torch.device(device) if isinstance(device, str) else device
+        self.num_concepts = int(num_concepts)
+        self.classes = list(Us)
+        if case is None:    # HeatmapGenerator's inference, from the class names
+            case = "toy" if all(c.endswith("1") or c.endswith("2") for c in self.classes) else "gtzan"
+        self.mapper = CLASS_IDX_MAPPER if case == "gtzan" else CLASS_IDX_MAPPER_TOY
+        self.num_classes = len(self.mapper)
+        for c in self.classes:
+            if c not in self.mapper:
+                raise ValueError(f"unknown class name {c!r} in Us (classes: {list(self.mapper)})")
+        mats = [torch.as_tensor(Us[c]) for c in self.classes]
+        for c, U in zip(self.classes, mats):
+            if U.dim() != 2 or U.size(0) != U.size(1) or U.shape != mats[0].shape:
+                raise ValueError(f"Us[{c!r}] has shape {tuple(U.shape)}; every matrix must be square and of the shape "
+                                 f"of Us[{self.classes[0]!r}], {tuple(mats[0].shape)}")
+        if self.num_concepts < 1 or mats[0].size(0) % self.num_concepts:
+            raise ValueError(f"num_concepts={num_concepts} must be a positive divisor of d={mats[0].size(0)}")
+        self.table_index = {c: i for i, c in enumerate(self.classes)}
+        self.projectionmodel = MultiProjectionModel(model, layer_idx, [U.to(self.device) for U in mats],
+                                                    self.num_concepts, case=case)
+        self.composite = get_class_composite(name_map, self.num_concepts, device=device, canonizers=canonizers)
+        self.info = {}
+        self.info_device = {}
+
+    def _indices(self, names: Sequence[str], table: Mapping[str, int], B: int, what: str) -> List[int]:
+        names = [names] * B if isinstance(names, str) else list(names)
+        if len(names) != B:
+            raise ValueError(f"{what} has {len(names)} entries for a batch of {B} rows")
+        for i, c in enumerate(names):
+            if c not in table:
+                raise ValueError(f"{what}[{i}] = {c!r} is not a known class (row {i}; known: {list(table)})")
+        return [table[c] for c in names]
+
+    def generate_subspace_heatmaps(self, input_batch: torch.Tensor, sample_classes: Sequence[str],
+                                   subspace_classes: Optional[Sequence[str]] = None, one_hot_encoded: bool = False,
+                                   to_host: bool = True) -> None:
+        x = input_batch.to(self.device, torch.float32).contiguous()
+        B = x.size(0)
+        cls = self._indices(sample_classes, self.mapper, B, "sample_classes")
+        rows = self._indices(sample_classes if subspace_classes is None else subspace_classes, self.table_index, B,
+                             "subspace_classes" if subspace_classes is not None else "sample_classes")
+        eng = get_engine(self.projectionmodel, self.composite)
+        out = eng.subspace_heatmaps(x, cls=torch.tensor(cls, dtype=torch.int32).to(self.device), one_hot=one_hot_encoded,
+                                    standard=self.standard, u_rows=rows)
+        self.info_device = out
+        if to_host:     # HeatmapGenerator's simple path: pinned buffers, the copies queued on the stream, one wait
+            info = {}
+            inp = input_batch.detach()
+            if inp.dtype == torch.bfloat16:
+                inp = inp.float()
+            if inp.device.type == "cpu":
+                info["input"] = inp.numpy()
+            else:
+                info["input"] = torch.empty(inp.shape, dtype=inp.dtype, pin_memory=True)
+                info["input"].copy_(inp, non_blocking=True)
+            for k, v in out.items():
+                info[k] = torch.empty(v.shape, dtype=v.dtype, pin_memory=True)
+                info[k].copy_(v, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+            self.info = {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in info.items()}
 
 
 def get_class_composite(name_map: List[Tuple[List[str], object]], num_concepts: int,

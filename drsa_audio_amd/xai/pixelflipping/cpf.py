@@ -19,7 +19,10 @@
 Heatmaps come from the HIP engine on device.  Where the reference builds one HeatmapGenerator per
 (projection matrix, attributed class) over the SAME class batch (interclass, cpf.py:155-163), the
 engine runs the forward once and all attributed classes as rows of one backward (per-row class
-seeds), since the forward does not depend on the attributed class.
+seeds), since the forward does not depend on the attributed class.  ``fused=True`` (extension;
+concept_flipping, interclass_concept_flipping) goes one step further: the per-class loop of
+HeatmapGenerators becomes MultiHeatmapGenerator passes over the whole batch, every row through its own
+class's matrix (one plan per layer and K instead of one per class); the results are the same bits.
 
 Reference defects handled (new D14-D16):
 * D10: ``generate_subspace_heatmaps(concept_flipping=True)`` returns None in the reference (its
@@ -53,7 +56,7 @@ import torch
 from ...engine import get_engine
 from ...utils.constants import CLASS_IDX_MAPPER, CLASS_IDX_MAPPER_TOY
 from ...utils.evaluation import load_projection_matrix
-from ..explain.explainer import HeatmapGenerator
+from ..explain.explainer import HeatmapGenerator, MultiHeatmapGenerator
 from .core import Flipper
 
 GTZAN_LAYERS = [1, 4, 7, 10, 13]
@@ -81,17 +84,61 @@ def _subspace_heatmaps(model, x, U, name_map, genre, K, layer_idx, device, cls_r
     return eng.subspace_heatmaps(x.to(device, torch.float32).contiguous(), cls=cls_rows)["subspace_heatmaps"]
 
 
+def _fused_class_heatmaps(model, x, spc, mapper, name_map, layer_idx, path_to_U, num_concepts, standard_r, device,
+                          Us) -> torch.Tensor:
+    """concept_flipping's heatmaps [n_classes * spc, K or 1, H, W] in one pass: block i attributed to class i
+    through class i's matrix (MultiHeatmapGenerator), instead of a HeatmapGenerator per class."""
+    tab = {g: torch.as_tensor(Us[g] if Us is not None else load_projection_matrix(g, layer_idx, path_to_U,
+                                                                                  device=device)) for g in mapper}
+    gen = MultiHeatmapGenerator(model, tab, name_map, num_concepts=num_concepts, layer_idx=layer_idx, device=device,
+                                case="toy" if mapper is CLASS_IDX_MAPPER_TOY else "gtzan")
+    gen.generate_subspace_heatmaps(x[:len(mapper) * spc], [g for g in mapper for _ in range(spc)], to_host=False)
+    return gen.info_device["standard_heatmaps" if standard_r else "subspace_heatmaps"]
+
+
+def _interclass_fused(model, x, spc, genres, name_map, path_to_U, toy, num_concepts, device, Us, layer_idcs,
+                      reference_indexing, flipper, fwd) -> List[np.ndarray]:
+    """interclass_concept_flipping with one MultiHeatmapGenerator (one plan) per layer holding every genre's matrix,
+    and one pass of it per subspace genre over the n class blocks."""
+    n, out = len(genres), []
+    attributed = [g for g in genres for _ in range(spc)]
+    for layer_idx in layer_idcs:
+        tab = {g: torch.as_tensor(Us[layer_idx][g] if Us is not None else
+                                  load_projection_matrix(g, layer_idx, path_to_U, device=device)) for g in genres}
+        # the per-class reference-indexing path runs the engine's default standard="sum", the other one
+        # HeatmapGenerator's "clone": the same here, so that the results are the same bits
+        gen = MultiHeatmapGenerator(model, tab, name_map, num_concepts=num_concepts, layer_idx=layer_idx, device=device,
+                                    standard="sum" if reference_indexing else "clone", case="toy" if toy else "gtzan")
+        aupcs = []
+        for i, sub_genre in enumerate(genres):
+            # block j: class batch i (reference indexing, D14) or class batch j, attributed to genre j, through U_i
+            xb = x[i * spc:(i + 1) * spc].repeat(n, 1, 1, 1) if reference_indexing else x[:n * spc]
+            gen.generate_subspace_heatmaps(xb, attributed, [sub_genre] * (n * spc), to_host=False)
+            aupc, _, _ = flipper(fwd, x, gen.info_device["subspace_heatmaps"])
+            aupcs.append(aupc.mean(axis=-1))
+        out.append(np.stack(aupcs, axis=0))
+    return out
+
+
 def concept_flipping(model, input_batch, name_map, layer_idx, path_to_U: Optional[str] = None,
                      num_concepts: int = 4, standard_r: bool = False, case=None,
                      device=torch.device("cuda"), Us: Optional[Dict[str, torch.Tensor]] = None,
-                     perturbation_size: int = 16, forward_func=None, return_heatmaps: bool = False):
+                     perturbation_size: int = 16, forward_func=None, return_heatmaps: bool = False,
+                     fused: bool = False):
     """cpf.py:20-84.  ``Us`` (extension) maps class names to matrices instead of a directory of DRSA
-    runs; ``return_heatmaps`` also returns the flipped heatmaps [B, K, H, W] (device)."""
+    runs; ``return_heatmaps`` also returns the flipped heatmaps [B, K, H, W] (device); ``fused``
+    (extension): all class blocks in one MultiHeatmapGenerator pass, the same results."""
     if isinstance(input_batch, np.ndarray):
         input_batch = torch.tensor(input_batch)
     mapper = _mapper(case)
     x = input_batch.to(device)
     spc = x.size(0) // len(mapper)
+    if fused:
+        R = _fused_class_heatmaps(model, x, spc, mapper, name_map, layer_idx, path_to_U, num_concepts, standard_r,
+                                  device, Us)
+        out = Flipper(perturbation_size=perturbation_size, device=device)(
+            forward_func if forward_func is not None else _model_forward(model), x, R)
+        return (out + (R,)) if return_heatmaps else out
     heatmaps = []
     for i, genre in enumerate(mapper):
         U = Us[genre] if Us is not None else load_projection_matrix(genre, layer_idx, path_to_U, device=device)
@@ -111,10 +158,12 @@ def interclass_concept_flipping(model, input_batch, name_map, path_to_U: Optiona
                                 standard_r: bool = False, toy: bool = False, num_concepts: int = 4,
                                 device=torch.device("cuda"), Us: Optional[Dict[int, Dict[str, torch.Tensor]]] = None,
                                 layer_idcs: Sequence[int] = tuple(GTZAN_LAYERS), reference_indexing: bool = True,
-                                perturbation_size: int = 16, forward_func=None) -> List[np.ndarray]:
+                                perturbation_size: int = 16, forward_func=None, fused: bool = False) -> List[np.ndarray]:
     """cpf.py:87-181: for every layer, the [n_classes, n_classes] matrix of class-mean AUPCs whose
     row i uses the projection matrix of genre i and whose column j attributes genre j (D14 on
-    which class batch is attributed).  ``Us[layer][genre]`` (extension) replaces the run directory."""
+    which class batch is attributed).  ``Us[layer][genre]`` (extension) replaces the run directory.
+    ``fused`` (extension): one MultiHeatmapGenerator per layer holding every genre's matrix, and one pass of it
+    per subspace genre, instead of a HeatmapGenerator (and a plan) per (subspace genre, attributed genre)."""
     if isinstance(input_batch, np.ndarray):
         input_batch = torch.tensor(input_batch)
     mapper = {"class1": 0, "class2": 1} if toy else CLASS_IDX_MAPPER
@@ -125,6 +174,9 @@ def interclass_concept_flipping(model, input_batch, name_map, path_to_U: Optiona
     flipper = Flipper(perturbation_size=perturbation_size, device=device)
     fwd = forward_func if forward_func is not None else _model_forward(model)
     out = []
+    if fused:
+        return _interclass_fused(model, x, spc, genres, name_map, path_to_U, toy, num_concepts, device, Us, layer_idcs,
+                                 reference_indexing, flipper, fwd)
     for layer_idx in layer_idcs:
         aupcs = []
         for i, sub_genre in enumerate(genres):

@@ -417,6 +417,21 @@ int drsa_amd_projection_bwd(const float* gp, const uint8_t* amax, const float* a
                             const float* den, const float* U, const float* P, float* G, int B, int D, int H, int W,
                             int K, float eps_proj, float eps_den, int fanout, void* stream);
 
+/* The two calls above with a matrix per row (mixed-class batches: one DRSA matrix per class).
+ * U_tab and P_tab are [n_u][D][D] (each P by drsa_amd_projection_residual); u_row is device int32 [B], one
+ * entry per row of a (fanout == 0: per replicated row), and row b runs on matrix u_row[b].  Row b of every
+ * output is, bit for bit, what the single-matrix call gives for that row alone with U_tab[u_row[b]].  The
+ * kernels clamp an index into [0, n_u - 1], so a bad one reads a wrong matrix of the table, never outside it;
+ * validating u_row is the caller's (it is device data).  U_tab, P_tab, u_row non-NULL, n_u >= 1 and
+ * 1 <= D <= 128 are required (DRSA_EINVAL), then every check of the single-matrix call. */
+int drsa_amd_projection_fwd_multi(const float* a, const float* U_tab, const float* P_tab, const int* u_row, int n_u,
+                                  float* h, float* ap, float* pooled, uint8_t* amax, int B, int D, int H, int W,
+                                  int pool, void* stream);
+int drsa_amd_projection_bwd_multi(const float* gp, const uint8_t* amax, const float* ap, const float* h,
+                                  const float* a, const float* den, const float* U_tab, const float* P_tab,
+                                  const int* u_row, int n_u, float* G, int B, int D, int H, int W, int K,
+                                  float eps_proj, float eps_den, int fanout, void* stream);
+
 /* AlphaBeta on a conv with non-negative input (zennit AlphaBeta as configured at pf.py:285-289,
  * restated in oracle/lrp_ref.py): split R at the conv output into gp = R / stab(den_p) and
  * gn = R / stab(den_n) (den per sample, R rows = sample*clones + clone, n elements per row) ... */
