@@ -128,6 +128,10 @@ SIGNATURES = {
     "drsa_amd_mel_to_audio": (_i32, [_fp, _fp, _fp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp,
                                      _vp]),
     "drsa_amd_audio_normalize": (_i32, [_fp, _i64, _i32, _fp, _i64, _i32, _i32, _vp]),
+    "drsa_amd_mel_relevance_to_stft": (_i32, [_fp, _fp, _fp, _i64, _i32, _i32, _i32, _i32, _ip, _ip, _ip, _fp, _i32,
+                                              _f32, _fp, _vp]),
+    "drsa_amd_heatmap_mask_large": (_i32, [_fp, _i64, _i32, _i32, _i32, _i32, _i32, _fp, _i32, _fp, _vp]),
+    "drsa_amd_stft_mask_to_audio": (_i32, [_fp, _fp, _i64, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _vp]),
 }
 
 class DrsaProblem(C.Structure):

@@ -97,7 +97,11 @@ class Loader:
                                  self.sample_rate)
             lo, n, off, w = fbank_bands(fb)
             pinv = torch.from_numpy(mel_pinv(fb)).to(torch.float32)          # [n_freqs, n_mels]
+            # the same bank bin by bin (the bands that cover each bin, ascending): drsa_amd_mel_relevance_to_stft
+            blo, bn, boff, bw = fbank_bands(fb.t().contiguous())
             self._tables[key] = {
+                "bin_lo": blo.to(device), "bin_n": bn.to(device), "bin_off": boff.to(device), "bin_w": bw.to(device),
+                "bin_nnz": int(bw.numel()),
                 "window": torch.hann_window(self.n_fft).to(device),
                 "lo": lo.to(device), "n": n.to(device), "off": off.to(device), "w": w.to(device),
                 "nnz": int(w.numel()), "fb": fb,

@@ -15,6 +15,12 @@ For one source chunk and its heatmaps (DESIGN.md "Concept audio"):
 4. synthesis   ``istft(mag * phase)``: window, overlap-add, window-envelope division, centre trim.
 5. normalise   ``peak_normalizer`` per audio, then ``adjust_vol`` against the source waveform.
 
+``resolution="stft"`` (DESIGN.md "Concept audio at STFT resolution", ``csrc/stft_audio.hip``) renders
+the same heatmaps on the linear-frequency axis instead: the analysis is the model's own front end
+(frames 1..width, power 1), the heatmaps are lifted through the filterbank onto the STFT bins
+(``lift_to_stft``, an LRP z-rule), masked there, and the audio is ``istft(mask * X)``: no
+pseudo-inverse, and an all-ones mask returns the chunk itself.
+
 Everything returns device tensors; there is no CPU path.
 """
 from __future__ import annotations
@@ -79,15 +85,21 @@ def _as_device(x, device: torch.device) -> torch.Tensor:
 
 def heatmap_masks(heatmaps: torch.Tensor, smoother: Optional[GaussianBlur], rank_first: int, rank_rest: int,
                   group: int = 1) -> torch.Tensor:
-    """``drsa_amd_heatmap_mask`` over maps [..., H, W] (device, float32, contiguous)."""
+    """``drsa_amd_heatmap_mask`` over maps [..., H, W] (device, float32, contiguous); maps that
+    do not fit its LDS (the entry answers DRSA_EUNSUPPORTED) go to ``drsa_amd_heatmap_mask_large``,
+    whose results are bit-identical wherever both run."""
     _capi.require_gpu(heatmaps, "heatmap", dtype=torch.float32)
     smoother = smoother if smoother is not None else GaussianBlur(1, 1.0)
     H, W = heatmaps.shape[-2:]
     n_maps = heatmaps.numel() // (H * W)
     out = torch.empty_like(heatmaps)
-    _capi.call("drsa_amd_heatmap_mask", heatmaps.data_ptr(), n_maps, H, W, group, rank_first, rank_rest,
-               smoother.taps(heatmaps.device).data_ptr(), smoother.kernel_size, out.data_ptr(),
-               _capi.stream_ptr(heatmaps.device))
+    args = (heatmaps.data_ptr(), n_maps, H, W, group, rank_first, rank_rest, smoother.taps(heatmaps.device).data_ptr(),
+            smoother.kernel_size, out.data_ptr(), _capi.stream_ptr(heatmaps.device))
+    rc = _capi.lib().drsa_amd_heatmap_mask(*args)
+    if rc == _capi.DRSA_EUNSUPPORTED:
+        _capi.call("drsa_amd_heatmap_mask_large", *args)
+    else:
+        _capi.check(rc, "drsa_amd_heatmap_mask")
     return out
 
 
@@ -189,15 +201,82 @@ class Mel2Audio:
         ph = torch.as_tensor(phase).to(dev, torch.complex64)
         return self._synthesise(mel[None], ph.t().contiguous()[None], mask[None, None])[0, 0]
 
+    # ------------------------------------------------------- STFT resolution
+    def _require_model_shape(self, H: int, W: int) -> None:
+        if (H, W) != (self.n_mels, self.width):
+            raise ValueError(f"heatmaps are {H}x{W} but the model input is {self.n_mels}x{self.width}")
+
+    def analyse_stft(self, wavs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """wavs [B, L] (not yet peak-normalised) -> mel [B, n_mels, width], X [B, width, n_freq]
+        (complex) of the model's own front end, whatever the class: frames 1..width of the
+        peak-normalised chunk, power 1 (``Loader.transform_wav``'s log-mel is log10 of this mel + 1e-7)."""
+        return self.loader.analyse(wavs, frame0=1, width=self.width, power=1, peak_norm=True)
+
+    def lift_to_stft(self, heatmaps: torch.Tensor, mel: torch.Tensor, X: torch.Tensor, eps: float = 1e-7
+                     ) -> torch.Tensor:
+        """Relevance at the log-mel input -> relevance on the STFT bins (``drsa_amd_mel_relevance_to_stft``):
+        heatmaps [B, C, n_mels, width], mel and X as ``analyse_stft`` returns them -> [B, C, n_freq, width].
+        An LRP z-rule through the filterbank; log10, the clamp and the normalisation are elementwise
+        and pass relevance unchanged, the log offset ``eps`` absorbs:
+        ``R_stft[f, t] = |X[t, f]| sum_m fb[f, m] R[m, t] / (mel[m, t] + eps)``."""
+        for name, t in (("heatmaps", heatmaps), ("mel", mel)):
+            _capi.require_gpu(t, name, dtype=torch.float32)
+        _capi.require_gpu(X, "X", dtype=torch.complex64)
+        B, n_mels, width = mel.shape
+        n_freq = self.n_fft // 2 + 1
+        if heatmaps.dim() != 4 or (heatmaps.size(0), *heatmaps.shape[2:]) != (B, n_mels, width) \
+                or tuple(X.shape) != (B, width, n_freq) or n_mels != self.n_mels:
+            raise ValueError(f"lift_to_stft: heatmaps {tuple(heatmaps.shape)}, mel {tuple(mel.shape)} and "
+                             f"X {tuple(X.shape)} do not fit each other or the {self.n_mels} x {n_freq} filterbank")
+        C = heatmaps.size(1)
+        t = self.loader.tables(mel.device)
+        out = torch.empty(B, C, n_freq, width, device=mel.device)
+        _capi.call("drsa_amd_mel_relevance_to_stft", heatmaps.data_ptr(), mel.data_ptr(),
+                   torch.view_as_real(X).data_ptr(), B, C, n_mels, width, n_freq, t["bin_lo"].data_ptr(),
+                   t["bin_n"].data_ptr(), t["bin_off"].data_ptr(), t["bin_w"].data_ptr(), t["bin_nnz"], float(eps),
+                   out.data_ptr(), _capi.stream_ptr(mel.device))
+        return out
+
+    def stft_heatmaps(self, standard_heatmaps, subspace_heatmaps=None, wavs=None) -> torch.Tensor:
+        """Heatmaps on the linear-frequency axis: the arguments of ``make_audios_batch`` (a
+        ``HeatmapGenerator.info`` dict is accepted too) -> [B, K+1, n_freq, width], map 0 the standard
+        heatmap's.  Column t is STFT frame t + 1 of the peak-normalised chunk."""
+        std, sub, wavs = self._batch_inputs(standard_heatmaps, subspace_heatmaps, wavs)
+        self._require_model_shape(*sub.shape[-2:])
+        mel, X = self.analyse_stft(wavs)
+        return self.lift_to_stft(torch.cat([std, sub], dim=1), mel, X)
+
+    def stft_masks_to_audio(self, X: torch.Tensor, masks: torch.Tensor) -> torch.Tensor:
+        """X [B, width, n_freq] complex, masks [B, C, n_freq, width] -> un-normalised audio
+        [B, C, hop (width - 1)] = istft(mask * X) (``drsa_amd_stft_mask_to_audio``)."""
+        _capi.require_gpu(X, "X", dtype=torch.complex64)
+        _capi.require_gpu(masks, "masks", dtype=torch.float32)
+        B, width, n_freq = X.shape
+        if masks.dim() != 4 or (masks.size(0), *masks.shape[2:]) != (B, n_freq, width) or n_freq != self.n_fft // 2 + 1:
+            raise ValueError(f"stft_masks_to_audio: masks {tuple(masks.shape)} do not fit X {tuple(X.shape)} "
+                             f"(n_fft {self.n_fft})")
+        C = masks.size(1)
+        t = self.loader.tables(X.device)
+        env = self.envelope(X.device, width)
+        out = torch.empty(B, C, self.hop_length * (width - 1), device=X.device)
+        _capi.call("drsa_amd_stft_mask_to_audio", torch.view_as_real(X).data_ptr(), masks.data_ptr(), B, C, self.n_fft,
+                   self.hop_length, width, t["window"].data_ptr(), env.data_ptr(), out.data_ptr(),
+                   _capi.stream_ptr(X.device))
+        return out
+
+    def normalise(self, audios: torch.Tensor, wavs: torch.Tensor) -> torch.Tensor:
+        """In place over audios [B, C, n] (``drsa_amd_audio_normalize``): ``peak_normalizer`` per
+        audio, then (``volume_match``) ``adjust_vol`` against the source's waveform wavs [B, L]."""
+        B, C, n = audios.shape
+        _capi.call("drsa_amd_audio_normalize", audios.data_ptr(), B * C, n,
+                   wavs.data_ptr() if self.volume_match else None, wavs.size(-1), wavs.size(-1), C,
+                   _capi.stream_ptr(audios.device))
+        return audios
+
     # ------------------------------------------------------------ end to end
-    def make_audios_batch(self, standard_heatmaps, subspace_heatmaps=None, wavs=None, percentile=50) -> torch.Tensor:
-        """The batched ``make_audios``: standard_heatmaps [B, H, W] (or a ``HeatmapGenerator.info``
-        dict holding both kinds), subspace_heatmaps [B, K, H, W], wavs [B, L] (as passed to
-        ``make_audios``: not yet peak-normalised) -> [B, K+1, hop (width - 1)].  One analysis, one
-        mask, one synthesis and one normalisation launch for the whole batch.  Audio 0 of a source
-        is its standard heatmap's (always percentile 50, as the reference), audios 1..K its
-        concepts' (``percentile``); each is peak-normalised and, for ``Mel2Audio``, brought to the
-        RMS of the waveform that was passed in and clamped to [-1, 1]."""
+    def _batch_inputs(self, standard_heatmaps, subspace_heatmaps, wavs):
+        """The arguments of ``make_audios_batch`` as device tensors: std [B, 1, H, W], sub [B, K, H, W],
+        wavs [B, L]."""
         if isinstance(standard_heatmaps, dict):
             info = standard_heatmaps
             standard_heatmaps, subspace_heatmaps = info["standard_heatmaps"], info["subspace_heatmaps"]
@@ -210,21 +289,44 @@ class Mel2Audio:
         std = std.reshape(B, 1, H, W)
         if wavs.size(0) != B:
             raise ValueError(f"{B} sources of heatmaps but {wavs.size(0)} waveforms")
+        return std, sub, wavs
+
+    def make_audios_batch(self, standard_heatmaps, subspace_heatmaps=None, wavs=None, percentile=50,
+                          resolution: str = "mel") -> torch.Tensor:
+        """The batched ``make_audios``: standard_heatmaps [B, H, W] (or a ``HeatmapGenerator.info``
+        dict holding both kinds), subspace_heatmaps [B, K, H, W], wavs [B, L] (as passed to
+        ``make_audios``: not yet peak-normalised) -> [B, K+1, hop (width - 1)].  One analysis, one
+        mask, one synthesis and one normalisation launch for the whole batch.  Audio 0 of a source
+        is its standard heatmap's (always percentile 50, as the reference), audios 1..K its
+        concepts' (``percentile``); each is peak-normalised and, for ``Mel2Audio``, brought to the
+        RMS of the waveform that was passed in and clamped to [-1, 1].
+
+        ``resolution="stft"``: the four STFT-resolution stages instead (``analyse_stft``,
+        ``lift_to_stft``, ``heatmap_masks`` on the [n_freq, width] maps, ``stft_masks_to_audio``),
+        then the same normalisation.  Output sample s is chunk sample s + hop."""
+        if resolution not in ("mel", "stft"):
+            raise ValueError(f'resolution must be "mel" or "stft", got {resolution!r}')
+        std, sub, wavs = self._batch_inputs(standard_heatmaps, subspace_heatmaps, wavs)
+        B, K, H, W = sub.shape
+        if resolution == "stft":
+            self._require_model_shape(H, W)
+            mel, X = self.analyse_stft(wavs)
+            maps = self.lift_to_stft(torch.cat([std, sub], dim=1), mel, X)
+            n = maps.size(-2) * maps.size(-1)
+            masks = heatmap_masks(maps, self.smoother, percentile_rank(50, n),
+                                  percentile_rank(percentile, n) if percentile else -1, group=K + 1)
+            return self.normalise(self.stft_masks_to_audio(X, masks), wavs)
         mel, X = self._analyse(wavs, peak_norm=True)
         if (H, W) != tuple(mel.shape[1:]):
             raise ValueError(f"heatmaps are {H}x{W} but the mel is {mel.size(1)}x{mel.size(2)}")
         n = H * W
         masks = heatmap_masks(torch.cat([std, sub], dim=1), self.smoother, percentile_rank(50, n),
                               percentile_rank(percentile, n) if percentile else -1, group=K + 1)
-        out = self._synthesise(mel, X, masks)
-        _capi.call("drsa_amd_audio_normalize", out.data_ptr(), B * (K + 1), out.size(-1),
-                   wavs.data_ptr() if self.volume_match else None, wavs.size(-1), wavs.size(-1), K + 1,
-                   _capi.stream_ptr(dev))
-        return out
+        return self.normalise(self._synthesise(mel, X, masks), wavs)
 
     def make_audios(self, sample_info: Dict[str, Union[np.ndarray, torch.Tensor]], original_audio=None,
                     startpoint=None, num_concepts: int = 4, percentile=50, path_to_sample: Optional[str] = None,
-                    sample_idx: int = 0) -> List[torch.Tensor]:
+                    sample_idx: int = 0, resolution: str = "mel") -> List[torch.Tensor]:
         """audiogen.py:53-112: the list [standard, concept 0, ..., concept num_concepts-1] of
         explanation audios of one sample -- the B = 1 case of ``make_audios_batch``.
         ``sample_info`` holds ``standard_heatmap`` [H, W] (or ``standard_heatmaps`` [B, H, W], as
@@ -249,7 +351,7 @@ class Mel2Audio:
             std, sub = std.reshape(-1, H, W)[sample_idx], sub[sample_idx]
         std, sub = std.reshape(1, H, W), sub.reshape(-1, H, W)[:num_concepts][None]
         wav = torch.as_tensor(np.asarray(wav) if not torch.is_tensor(wav) else wav).reshape(1, -1)
-        return list(self.make_audios_batch(std, sub, wav, percentile=percentile)[0])
+        return list(self.make_audios_batch(std, sub, wav, percentile=percentile, resolution=resolution)[0])
 
 
 class Mel2AudioToy(Mel2Audio):

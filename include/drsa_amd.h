@@ -674,6 +674,44 @@ int drsa_amd_mel_to_audio(const float* mel, const float* X, const float* mask, i
 int drsa_amd_audio_normalize(float* audio, int64_t n_audio, int len, const float* wav, int64_t wav_stride,
                              int wav_len, int C, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Concept audio at STFT resolution: relevance through the mel filterbank.  csrc/stft_audio.hip.
+ * mel and X are drsa_amd_stft_mel_phase's outputs with power = 1 (the model's front end:
+ * frame0 = 1); X must be 8-byte aligned.
+ * ------------------------------------------------------------------------- */
+
+/* The LRP z-rule through the filterbank, for n_src sources and the C maps of each:
+ *   q[m][t] = relevance[m][t] / (mel[m][t] + eps)          (one add, one IEEE division; eps > 0)
+ *   a[f][t] = sum over the bands m that cover bin f, ascending m, one fmaf chain from 0, of fb[f][m] q[m][t]
+ *   out[f][t] = |X[t][f]| a[f][t]
+ * The filterbank comes bin by bin (the transposed band form of drsa_amd_logmel's tables): bin f is
+ * covered by bands bin_lo[f] .. bin_lo[f]+bin_n[f]-1 with weights bin_w[bin_off[f] ..] (bin_nnz in all).
+ *   relevance [n_src, C, n_mels, width];  mel [n_src, n_mels, width];  X [n_src, width, n_freq, 2];
+ *   out [n_src, C, n_freq, width].
+ * A source's maps are bit-identical in any batch.  DRSA_EUNSUPPORTED when the 32-frame tiles
+ * (n_freq x 33 + 2 x n_mels x 32 floats and the tables) exceed 160 KB of LDS. */
+int drsa_amd_mel_relevance_to_stft(const float* relevance, const float* mel, const float* X, int64_t n_src, int C,
+                                   int n_mels, int width, int n_freq, const int* bin_lo, const int* bin_n,
+                                   const int* bin_off, const float* bin_w, int bin_nnz, float eps, float* out,
+                                   void* stream);
+
+/* drsa_amd_heatmap_mask (same arguments, bit-identical results on every map both accept) with the
+ * map in global memory instead of LDS: for maps of up to H*W = 4 194 304 (2^22) elements, e.g.
+ * 401 x 128 or 513 x 512; DRSA_EUNSUPPORTED above that.  The threshold comes from integer
+ * counters only and no workgroup waits for another one. */
+int drsa_amd_heatmap_mask_large(const float* heatmaps, int64_t n_maps, int H, int W, int group, int rank_first,
+                                int rank_rest, const float* taps, int k, float* mask, void* stream);
+
+/* For each of n_src sources and its C masks: Y[t][f] = mask[f][t] X[t][f], then istft(Y, center=True)
+ * as drsa_amd_mel_to_audio: inverse real FFT (the imaginary parts of bins 0 and n_fft/2 dropped),
+ * * window, overlap-add at hop in ascending frame order, / envelope, n_fft/2 samples dropped at
+ * each end.  No mel, no pseudo-inverse: an all-ones mask returns the analysed signal.
+ *   X [n_src, width, n_fft/2+1, 2];  mask [n_src, C, n_fft/2+1, width];  audio [n_src, C, hop*(width-1)].
+ * An audio is bit-identical in any batch.  The transforms' shape rules hold; DRSA_EUNSUPPORTED
+ * when n_fft/hop overlaps more than 9 frames or the LDS need exceeds 160 KB. */
+int drsa_amd_stft_mask_to_audio(const float* X, const float* mask, int64_t n_src, int C, int n_fft, int hop,
+                                int width, const float* window, const float* envelope, float* audio, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,312 @@
+"""Concept audio at STFT resolution (csrc/stft_audio.hip, the ``resolution="stft"`` path of
+xai/explain/audiogen.py) vs the CPU oracle tests/stft_audio_ref.py (GPU).
+
+Tolerance: the project's anchored gates, imported from test_audiogen_gpu and not restated.  Maps
+(``anchored``): the maximum and the RMS of the error against the oracle's float64 chain at most
+RATIO = 2 x those of its float32 chain ("torch32"), + the 1e-7 floor.  Audios (``audio_check``):
+each audio's relative L2 distance, median and worst, by the same rule.  Both sides of a stage test
+get the same float32 inputs (the kernels' own mel and X), so a stage is measured alone.  Kept
+sets, refusals and everything called "bit-identical" are exact comparisons.
+
+The cut of a mask is taken on a computed map, so a near-tie may fall on the other side in
+float64; the stages are therefore gated one by one, and the end-to-end tests check that the
+public call is exactly its four stages in sequence.
+"""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import audiogen_ref as R
+import fft_plan_cases as P
+import stft_audio_ref as S
+import test_audiogen_gpu as AG
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda")
+LENGTH = {"toy": 16000, "gtzan": 48000}
+
+
+def _dev(x):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(case, B, C):
+    """B sources x C heatmaps at a product geometry with the kernels' own analysis (read-only, shared)."""
+    g = S.GEOM[case]
+    m = AG._m2a(case)
+    wavs = R.signals(B, LENGTH[case], seed=11 + B)
+    rel = R.heatmaps(B, C, g["n_mels"], g["width"], seed=12 + C)
+    mel, X = m.analyse_stft(_dev(wavs))
+    return g, m, wavs, rel, mel, X
+
+
+def _lift_refs(rel, mel, X, g):
+    return [np.stack([S.lift(rel[b], mel[b].cpu(), X[b].t().cpu(), g, mode).numpy() for b in range(len(rel))])
+            for mode in ("f64", "torch32")]
+
+
+# ------------------------------------------------------------------------ lift
+@pytest.mark.parametrize("case,B,C", [("toy", 2, 3), ("gtzan", 1, 2)])
+def test_lift_anchored_and_conserving(case, B, C):
+    g, m, _, rel, mel, X = _case(case, B, C)
+    n_freq = g["n_fft"] // 2 + 1
+    assert mel.shape == (B, g["n_mels"], g["width"]) and X.shape == (B, g["width"], n_freq)
+    out = m.lift_to_stft(_dev(rel), mel, X)
+    assert out.shape == (B, C, n_freq, g["width"]) and out.is_cuda and out.dtype == torch.float32
+    ref, t32 = _lift_refs(rel, mel, X, g)
+    AG.anchored(out, ref, t32, f"{case} lift")
+    # no band covers bin 0 or the Nyquist bin
+    assert float(out[:, :, 0].abs().max()) == 0.0 == float(out[:, :, -1].abs().max())
+    # conservation: each frame's lifted relevance sums to sum_m R mel / (mel + eps), float64 right-hand side
+    rhs = np.stack([S.conserved(rel[b], mel[b].cpu()).numpy() for b in range(B)])
+    AG.anchored(out.double().sum(-2), rhs, t32.astype(np.float64).sum(-2), f"{case} lift, conservation")
+
+
+def test_lift_silent_half_gives_exact_zeros():
+    """A chunk whose second half is exact zeros: the frames that lie inside it have X = 0 and
+    mel = 0, q = R / eps is large but finite, and the lifted relevance is exactly 0."""
+    g, m = S.GEOM["toy"], AG._m2a("toy")
+    wavs = R.signals(1, 16000, seed=3)
+    wavs[:, 8000:] = 0.0
+    mel, X = m.analyse_stft(_dev(wavs))
+    rel = R.heatmaps(1, 3, 64, 64, seed=4)
+    out = m.lift_to_stft(_dev(rel), mel, X)
+    tz = -(-(8000 + g["n_fft"] // 2) // g["hop"]) - 1          # column t is frame t + 1, which starts at (t+1) hop - n_fft/2
+    assert 0 < tz < 60
+    assert float(mel[..., tz:].abs().max()) == 0.0 and float(mel[..., :tz - 2].min()) > 0
+    assert torch.isfinite(out).all()
+    assert float(out[..., tz:].abs().max()) == 0.0
+    assert float(out[..., :tz - 2].abs().amax((1, 2)).min()) > 0
+
+
+def test_lift_batch_independence():
+    g, m, _, rel, mel, X = _case("toy", 3, 3)
+    out = m.lift_to_stft(_dev(rel), mel, X)
+    for i in range(3):
+        one = m.lift_to_stft(_dev(rel[i:i + 1]), mel[i:i + 1].contiguous(), X[i:i + 1].contiguous())
+        assert torch.equal(out[i:i + 1], one), i
+
+
+# ------------------------------------------------------------------ large mask
+def _mask_entry(entry, h, k, sigma, rank_first, rank_rest, group=1):
+    from drsa_audio_amd import _capi
+    from drsa_audio_amd.xai.explain.audiogen import GaussianBlur
+    H, W = h.shape[-2:]
+    out = torch.empty_like(h)
+    _capi.call(entry, h.data_ptr(), h.numel() // (H * W), H, W, group, rank_first, rank_rest,
+               GaussianBlur(k, sigma).taps(DEV).data_ptr(), k, out.data_ptr(), _capi.stream_ptr(DEV))
+    return out
+
+
+def _rank(p, n):
+    from drsa_audio_amd.xai.explain.audiogen import percentile_rank
+    return percentile_rank(p, n) if p else -1
+
+
+@functools.lru_cache(maxsize=None)
+def _map(H, W, kind):
+    if kind == "few":
+        h = (np.round(np.random.default_rng(H).standard_normal((H, W)) * 2) / 2).astype(np.float32)
+    else:
+        h = R.heatmaps(1, 1, H, W, seed=H + W, absolute=kind == "absolute")[0, 0]
+    h.setflags(write=False)
+    return h
+
+
+MAPS = [(401, 128), (241, 64), (41, 61)]
+KINDS = ["signed", "absolute", "few"]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("H,W", MAPS)
+def test_large_mask_kept_set(H, W, kind):
+    h = _map(H, W, kind)
+    for p in (None, 50, 90, 97.5):
+        raw = _mask_entry("drsa_amd_heatmap_mask_large", _dev(h), 1, 1.0, _rank(p, H * W), _rank(p, H * W)).cpu().numpy()
+        keep = R.kept(h, p) & (h > 0)
+        assert np.array_equal(raw != 0, keep), p
+        assert np.array_equal(raw, np.where(keep, h, 0).astype(np.float32)), p
+        if kind == "absolute" and p:
+            assert 0 < keep.sum() < h.size * (100 - p) / 100 + 1    # the cut is inside the positive part
+
+
+@pytest.mark.parametrize("k,sigma", [(5, 1.0), (9, 2.0)])
+@pytest.mark.parametrize("H,W", MAPS)
+def test_large_mask_blur_anchored(H, W, k, sigma):
+    h = _map(H, W, "absolute")
+    r = _rank(90, H * W)
+    out = _mask_entry("drsa_amd_heatmap_mask_large", _dev(h), k, sigma, r, r)
+    AG.anchored(out, R.mask(h, 90, k, sigma, "f64"), R.mask(h, 90, k, sigma, "torch32"), f"large mask {H}x{W} k={k}")
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("H,W", MAPS[1:])
+def test_large_mask_equals_the_lds_kernel(H, W, kind):
+    h = _dev(_map(H, W, kind))
+    for p in (None, 50, 90, 97.5):
+        for k, sigma in ((1, 1.0), (5, 1.0), (9, 2.0)):
+            r = _rank(p, H * W)
+            a = _mask_entry("drsa_amd_heatmap_mask_large", h, k, sigma, r, r)
+            b = _mask_entry("drsa_amd_heatmap_mask", h, k, sigma, r, r)
+            assert torch.equal(a, b), (p, k)
+
+
+@pytest.mark.parametrize("H,W", [(401, 128), (41, 61)])
+def test_large_mask_alone_and_in_a_group(H, W):
+    """7 maps with group = 3: maps 0, 3, 6 are cut at percentile 50, the others at 90; each equals
+    the map run alone (where the map's tiles are spread over more workgroups)."""
+    h = _dev(np.stack([_map(H, W, KINDS[i % 3]) * (1 + i) for i in range(7)]))
+    r50, r90 = _rank(50, H * W), _rank(90, H * W)
+    out = _mask_entry("drsa_amd_heatmap_mask_large", h, 5, 1.0, r50, r90, group=3)
+    for i in range(7):
+        r = r50 if i % 3 == 0 else r90
+        assert torch.equal(out[i], _mask_entry("drsa_amd_heatmap_mask_large", h[i].contiguous(), 5, 1.0, r, r)), i
+
+
+def test_masks_route_by_size():
+    """generate_mask and heatmap_masks take a 401 x 128 map (the LDS entry refuses it) and give the
+    large entry's result; a 241 x 64 map still takes the LDS kernel's."""
+    from drsa_audio_amd import _capi
+    from drsa_audio_amd.xai.explain.audiogen import GaussianBlur, Mel2Audio, heatmap_masks
+    big, small = _dev(_map(401, 128, "signed")), _dev(_map(241, 64, "signed"))
+    with pytest.raises(_capi.DrsaAmdError, match=rf"rc={_capi.DRSA_EUNSUPPORTED}\)"):
+        _mask_entry("drsa_amd_heatmap_mask", big, 5, 1.0, -1, -1)
+    for h in (big, small):
+        r = _rank(90, h.numel())
+        want = _mask_entry("drsa_amd_heatmap_mask_large", h, 5, 1.0, r, r)
+        assert torch.equal(Mel2Audio.generate_mask(h, GaussianBlur(5, 1.0), 90), want)
+        assert torch.equal(heatmap_masks(h[None], GaussianBlur(5, 1.0), r, r)[0], want)
+
+
+# ------------------------------------------------------------------- synthesis
+@pytest.mark.parametrize("case", ["toy", "gtzan"])
+def test_all_ones_mask_returns_the_chunk(case):
+    """mask = 1: analysis and synthesis return the (peak-normalised) chunk's samples hop .. hop width."""
+    g, m, wavs, _, _, X = _case(case, 2, 2)
+    n_freq = g["n_fft"] // 2 + 1
+    out = m.stft_masks_to_audio(X, torch.ones(2, 1, n_freq, g["width"], device=DEV))[:, 0]
+    wn = wavs / np.abs(wavs).max(-1, keepdims=True)
+    want = wn[:, g["hop"]:g["hop"] * g["width"]].astype(np.float64)
+    _, X32 = S.analysis(wn, g, "torch32")
+    t32 = np.stack([S.synthesis(X32[b], torch.ones(1, n_freq, g["width"]), g, "torch32")[0].numpy() for b in range(2)])
+    AG.audio_check(out, want, t32, f"{case} all-ones mask")
+
+
+def _synthesis_case(m, g, X, B, C, seed):
+    """Random masks in [0, 1) on the kernel's own X: the kernel, the f64 chain and the float32 chain."""
+    n_freq = g["n_fft"] // 2 + 1
+    masks = np.random.default_rng(seed).uniform(0, 1, (B, C, n_freq, g["width"])).astype(np.float32)
+    out = m.stft_masks_to_audio(X, _dev(masks))
+    assert out.shape == (B, C, g["hop"] * (g["width"] - 1))
+    ref, t32 = (np.stack([S.synthesis(X[b].t().cpu(), masks[b], g, mode).numpy() for b in range(B)])
+                for mode in ("f64", "torch32"))
+    return out, ref, t32, _dev(masks)
+
+
+@pytest.mark.parametrize("case", ["toy", "gtzan"])
+def test_synthesis_random_masks(case):
+    g, m, _, _, _, X = _case(case, 2, 2)
+    out, ref, t32, _ = _synthesis_case(m, g, X, 2, 2, seed=7)
+    AG.audio_check(out, ref, t32, f"{case} synthesis")
+
+
+PLAN_ROWS = {p[0]: p for p in P.PLANS}
+GEOMETRIES = [P.OVERLAPS[1] + (11,), P.OVERLAPS[4] + (4,), P.OVERLAPS[8] + (1,)] + \
+    [PLAN_ROWS[n][0:1] + PLAN_ROWS[n][2:7] for n in (8, 30, 600)]
+
+
+@pytest.mark.parametrize("geo", GEOMETRIES, ids=[f"nfft{x[0]}hop{x[1]}" for x in GEOMETRIES])
+def test_synthesis_plans_overlaps_and_batch_independence(geo):
+    """The minimum width (64/33, width 2), an odd M (50/13), the deepest overlap (36/4: extra 8),
+    and the plans of n_fft 8 (one pass), 30 (radix 3 then 5, odd M) and 600 (partial last trips):
+    the oracle gate, and a batch of 3 sources x 2 masks equals each source run alone, bit for bit."""
+    from drsa_audio_amd.utils.dataloading import Loader
+    from drsa_audio_amd.xai.explain.audiogen import Mel2Audio
+    n_fft, hop, n_mels, width, _, rem = geo
+    g = S.geometry(n_fft, hop, n_mels, width, sr=P.SR)
+    m = Mel2Audio(loader=Loader(None, sample_rate=P.SR, n_fft=n_fft, hop_length=hop, n_mels=n_mels, slice_length=0,
+                                width=width, device=DEV), blur_kernel=P.blur_size(n_mels, width))
+    wav = np.random.default_rng(n_fft + hop).uniform(-1, 1, (3, P.chunk_len(hop, width, rem, frame0=1))).astype(np.float32)
+    _, X = m.analyse_stft(_dev(wav))
+    out, ref, t32, masks = _synthesis_case(m, g, X, 3, 2, seed=n_fft)
+    AG.audio_check(out, ref, t32, f"n_fft {n_fft} hop {hop} width {width}")
+    for i in range(3):
+        assert torch.equal(out[i:i + 1], m.stft_masks_to_audio(X[i:i + 1].contiguous(), masks[i:i + 1].contiguous())), i
+
+
+def test_synthesis_refuses_what_does_not_fit_the_lds():
+    from drsa_audio_amd._capi import DRSA_EUNSUPPORTED, DrsaAmdError
+    from drsa_audio_amd.utils.dataloading import Loader
+    from drsa_audio_amd.xai.explain.audiogen import Mel2Audio
+    m = Mel2Audio(loader=Loader(None, sample_rate=P.SR, n_fft=960, hop_length=360, n_mels=40, slice_length=0, width=9,
+                                device=DEV))
+    X = torch.zeros(1, 9, 481, dtype=torch.complex64, device=DEV)
+    with pytest.raises(DrsaAmdError, match=rf"rc={DRSA_EUNSUPPORTED}\).*LDS footprint \d+ B exceeds 160 KB"):
+        m.stft_masks_to_audio(X, torch.ones(1, 1, 481, 9, device=DEV))
+
+
+# ------------------------------------------------------------------ end to end
+@pytest.mark.parametrize("case,B,K", [("toy", 3, 2), ("gtzan", 2, 2)])
+def test_make_audios_batch_is_its_four_stages(case, B, K):
+    """Mel2AudioToy (peak-normalised audios) at the toy geometry, Mel2Audio (volume-matched) at
+    GTZAN's, where the 401 x 128 maps take the large mask kernel."""
+    from drsa_audio_amd.xai.explain.audiogen import Mel2Audio, heatmap_masks
+    g, m, wavs, rel, _, _ = _case(case, B, K + 1)
+    std, sub, w = _dev(rel[:, 0]), _dev(rel[:, 1:]), _dev(wavs)
+    out = m.make_audios_batch(std, sub, w, percentile=90, resolution="stft")
+    assert out.shape == (B, K + 1, g["hop"] * (g["width"] - 1)) and torch.isfinite(out).all()
+    mel, X = m.analyse_stft(w)
+    maps = m.lift_to_stft(_dev(rel), mel, X)
+    assert torch.equal(maps, m.stft_heatmaps(std, sub, w))
+    assert torch.equal(maps, m.stft_heatmaps({"standard_heatmaps": rel[:, 0], "subspace_heatmaps": rel[:, 1:]}, wavs=wavs))
+    n = maps.size(-2) * maps.size(-1)
+    masks = heatmap_masks(maps, m.smoother, _rank(50, n), _rank(90, n), group=K + 1)
+    # the standard map is cut at percentile 50 whatever `percentile` says, the concepts' at 90
+    assert torch.equal(masks[1, 0], Mel2Audio.generate_mask(maps[1, 0], m.smoother, 50))
+    assert torch.equal(masks[1, 2], Mel2Audio.generate_mask(maps[1, 2], m.smoother, 90))
+    stages = m.normalise(m.stft_masks_to_audio(X, masks), w)
+    assert torch.equal(out, stages)
+    peak = out.abs().amax(-1)
+    if m.volume_match:
+        o = out.double()
+        rms, want = o.pow(2).mean(-1).sqrt(), torch.from_numpy(wavs.astype(np.float64)).pow(2).mean(-1).sqrt()[:, None].to(DEV)
+        free = peak < 1.0                                   # where the clamp does not bite the RMS is the source's
+        assert bool((rms <= want * (1 + 1e-5)).all()) and float(peak.max()) <= 1.0
+        assert not free.any() or float((rms / want - 1).abs()[free].max()) <= 1e-5
+    else:
+        assert float(peak.min()) == 1.0 == float(peak.max())
+    # the default is the mel path, unchanged
+    assert torch.equal(m.make_audios_batch(std, sub, w, percentile=90),
+                       m.make_audios_batch(std, sub, w, percentile=90, resolution="mel"))
+
+
+def test_make_audios_is_the_single_source_batch():
+    _, m, wavs, rel, _, _ = _case("toy", 3, 3)
+    info = {"standard_heatmaps": rel[:, 0], "subspace_heatmaps": rel[:, 1:]}
+    audios = m.make_audios(info, wavs[2], num_concepts=2, percentile=90, sample_idx=2, resolution="stft")
+    batch = m.make_audios_batch(_dev(rel[2:3, 0]), _dev(rel[2:3, 1:]), _dev(wavs[2:3]), percentile=90, resolution="stft")
+    assert len(audios) == 3 and torch.equal(torch.stack(audios), batch[0])
+    assert not torch.equal(batch, m.make_audios_batch(_dev(rel[2:3, 0]), _dev(rel[2:3, 1:]), _dev(wavs[2:3]), percentile=90))
+
+
+def test_heatmaps_of_another_shape_are_refused():
+    _, m, wavs, rel, _, _ = _case("toy", 3, 3)
+    for bad in (rel[..., :63], rel[..., :63, :]):
+        with pytest.raises(ValueError, match="model input"):
+            m.make_audios_batch(_dev(bad[:, 0]), _dev(bad[:, 1:]), _dev(wavs), resolution="stft")
+        with pytest.raises(ValueError, match="model input"):
+            m.stft_heatmaps(_dev(bad[:, 0]), _dev(bad[:, 1:]), _dev(wavs))
+
+
+def test_silent_source_gives_nan_audios_and_leaves_its_neighbours():
+    _, m, wavs, rel, _, _ = _case("toy", 3, 3)
+    quiet = wavs.copy()
+    quiet[1] = 0.0
+    args = (_dev(rel[:, 0]), _dev(rel[:, 1:]))
+    out = m.make_audios_batch(*args, _dev(quiet), percentile=90, resolution="stft")
+    base = m.make_audios_batch(*args, _dev(wavs), percentile=90, resolution="stft")
+    assert torch.isnan(out[1]).all()
+    assert torch.equal(out[[0, 2]], base[[0, 2]]) and torch.isfinite(base).all()
