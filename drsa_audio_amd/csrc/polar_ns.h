@@ -90,6 +90,11 @@ constexpr size_t ns_scratch_floats() {
 // 0.75 e^2 (1 + e/3) < 7.6e-5.  1e-2 instead of 1e-4 saves one Newton-Schulz iteration per step
 // at C3 (5 -> 4) and at d = 128 (4 -> 3): 0.0391 -> 0.0358 ms (C3), 0.166 -> 0.155 ms (C5 joint),
 // with the 2 000-step C3 and 5 000-step C5 trajectories still inside their 1e-4 gates.
+// The second "last" clause of the loops below (err_prev < 1e-4 and err > err_prev / 4: rounding is the
+// floor) is unreachable at DP <= 64 with this value: err_prev < 1e-4 already gives DP * err_prev <
+// 6.4e-3 < 1e-2, so the loop ended one iteration earlier.  At DP = 128 it can fire only for err_prev
+// in [1e-2 / 128, 1e-4) = [7.8e-5, 1e-4).  No case of tests/polar_ref.py's tables reaches it
+// (tests/test_polar_cases_cpu.py asserts that of the float32 model).
 #ifndef DRSA_NS_LAST
 #define DRSA_NS_LAST 1e-2f
 #endif

@@ -60,7 +60,15 @@ int drsa_amd_drsa_partial(const float* A, const float* C, int64_t N, int d, int 
 
 /* f_out[0] = objective f(U) (objective_fn, drsa.py:224-238); unless objective_only,
  * U_out = polar(U + grad f(U)) (orthogonalize, drsa.py:201-221, on device).
- * iters_out (nullable, device int) receives the Newton-Schulz iteration count. */
+ * iters_out (nullable, device int) receives the Newton-Schulz iteration count; 40 (the iteration
+ * limit, see drsa_amd_polar) means U + grad f(U) was singular or nearly so and U_out is finite but not
+ * orthogonal (e.g. a zero column of U: its gradient is zero, so it stays one).
+ * A concept with no relevance at all (S_k = 0: every relu block sum of concept k is 0) gets the
+ * column scale c_k = 0, so its columns of U enter the polar unchanged; f counts its M_k = 0.  The
+ * reference's autograd yields NaN there (0 * inf); 0 is this library's contract, pinned by the
+ * dead_concept cases of tests/test_polar_paths_gpu.py.  Every run loop (drsa_amd_drsa_run, _run_multi,
+ * _run_batched, _any_run) computes the same bits as this entry point does on the slab of the partial
+ * entry point of the same geometry and dtype. */
 int drsa_amd_drsa_finish(const float* gs, int64_t N_total, int d, int K, const float* U, float* U_out,
                          float* f_out, int objective_only, int* iters_out, void* stream);
 
@@ -157,7 +165,13 @@ int drsa_amd_debug_coop_spin_budget(long long ticks);
  * max|.|; the typical spread-out error of V = U + G is ~sqrt(d) smaller), or when fp32 rounding is
  * the floor.  So the tolerance is advisory for that last update: orthogonality of the result is the
  * bound above, gated in tests/test_drsa_gpu.py at |U^T U - I| < 2e-6 (step) and 5e-6 (d = 128
- * orthogonalize) and by the DRSA trajectories against the reference's fp64 eigh at 1e-4. */
+ * orthogonalize), by the DRSA trajectories against the reference's fp64 eigh at 1e-4, and in
+ * tests/test_polar_paths_gpu.py on ill-scaled and ill-conditioned V (both scaling branches, every
+ * exit, 0 to 40 iterations) at 5e-6, with U within 5e-5 of the float64 polar up to condition 1e3.
+ * The loop also ends after 40 iterations whatever the error: iters_out (nullable, device int)
+ * receives the count, and iters_out == 40 is how a caller sees that V did not converge (a singular
+ * or nearly singular V: U_out is then finite but not orthogonal; a converged call reports 40 only if
+ * its last update was the 40th, which takes a condition number of about 1e6). */
 int drsa_amd_polar(const float* V, int d, float* U_out, int* iters_out, void* stream);
 
 /* compute_subspace_relevances (explainer.py:206-242): out[b][k] = sum_n sum_{j in block k}

@@ -169,3 +169,51 @@ def check_slab(gs, Gt, S, d, K, tag=""):
     np.testing.assert_allclose(Sk, S, rtol=2e-5, atol=1e-6 * S.max())
     assert nonzero_pad == 0
     return dev_g, dev_s
+
+
+def explicit_loop(Ag, Cg, Ug, K, steps, natural=False, want_iters=False):
+    """The optimiser spelt out on the current stream: per step one call of the partial entry point and
+    one of the ONE-WORKGROUP finish (drsa_amd_drsa_partial + drsa_amd_drsa_finish, or their
+    drsa_amd_drsa_any_* namesakes with natural=True), then the objective at the last U.  This is what
+    drsa_run / _run_joint / _run_batched (fused step, cooperative finish, batched finish) must equal
+    bit for bit.  Returns (f [steps + 1], U_S) as device tensors, synchronised; with want_iters also a
+    dict: "iters" (iters_out of every step's polar), "gs0" (the reduced slab of step 0, float32
+    numpy) and "U1" (U after step 0)."""
+    import torch
+    from drsa_audio_amd import _capi
+    from drsa_audio_amd.xai.drsa.drsa import DrsaWorkspace
+    dev = Ag.device
+    N, d = Ag.shape
+    pre = "drsa_amd_drsa_any_" if natural else "drsa_amd_drsa_"
+    if natural:
+        nbytes = _capi.lib().drsa_amd_drsa_any_workspace_bytes(N, d, K)
+        assert nbytes > 0
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws_ptr, ws_bytes = buf.data_ptr(), buf.numel()
+        gs = torch.empty(_capi.lib().drsa_amd_drsa_any_slab_floats(d, K), device=dev)
+    else:
+        ws = DrsaWorkspace(N, d, K, dev)
+        ws_ptr, ws_bytes, gs = ws.ptr, ws.nbytes, ws.gs
+    st = _capi.stream_ptr(dev)
+    f = torch.empty(steps + 1, device=dev)
+    its = torch.full((steps + 1,), -1, dtype=torch.int32, device=dev)
+    extra = {}
+    U = Ug.clone()
+    for t in range(steps + 1):
+        _capi.call(pre + "partial", Ag.data_ptr(), Cg.data_ptr(), N, d, K, U.data_ptr(), gs.data_ptr(), ws_ptr,
+                   ws_bytes, st)
+        if t == 0 and want_iters:
+            extra["gs0"] = gs.clone()
+        U_new = torch.empty_like(U)
+        _capi.call(pre + "finish", gs.data_ptr(), N, d, K, U.data_ptr(), U_new.data_ptr(), f[t:].data_ptr(),
+                   1 if t == steps else 0, its[t:].data_ptr() if want_iters and t < steps else None, st)
+        if t < steps:
+            U = U_new
+            if t == 0 and want_iters:
+                extra["U1"] = U_new
+    torch.cuda.synchronize()
+    if not want_iters:
+        return f, U
+    extra["iters"] = [int(v) for v in its[:steps].cpu()]
+    extra["gs0"] = extra["gs0"].cpu().numpy()
+    return f, U, extra

@@ -151,7 +151,7 @@ def test_run_equals_partial_finish_loop_bitwise_graph_and_eager(d, K):
     """drsa_run -> drsa_amd_drsa_any_run (graph-replayed; the cooperative finish at DP = 128)
     equals the explicit loop of drsa_amd_drsa_any_partial and the one-workgroup
     drsa_amd_drsa_any_finish bit for bit; graph and eager runs and two runs are identical."""
-    from drsa_audio_amd import _capi
+    from drsa_slab_ref import explicit_loop
     from drsa_audio_amd.xai.drsa.drsa import drsa_run
     N, steps = N_STEP, 6
     A, C, U0, _, _ = ar.problem(N, d, K)
@@ -162,20 +162,7 @@ def test_run_equals_partial_finish_loop_bitwise_graph_and_eager(d, K):
         U_e, t_e = drsa_run(Ag, Cg, Ug, K, steps, use_graph=False)
         U_2, t_2 = drsa_run(Ag, Cg, Ug, K, steps, use_graph=True)
     torch.cuda.synchronize()
-    ws = _any_ws(N, d, K)
-    gs = torch.empty(ar.slab_floats(d, K), device=DEV)
-    st = _capi.stream_ptr()
-    f = torch.empty(steps + 1, device=DEV)
-    U = Ug.clone()
-    for t in range(steps + 1):
-        _capi.call("drsa_amd_drsa_any_partial", Ag.data_ptr(), Cg.data_ptr(), N, d, K, U.data_ptr(), gs.data_ptr(),
-                   ws.data_ptr(), ws.numel(), st)
-        U_new = torch.empty_like(U)
-        _capi.call("drsa_amd_drsa_any_finish", gs.data_ptr(), N, d, K, U.data_ptr(), U_new.data_ptr(),
-                   f[t:].data_ptr(), 1 if t == steps else 0, None, st)
-        if t < steps:
-            U = U_new
-    torch.cuda.synchronize()
+    f, U = explicit_loop(Ag, Cg, Ug, K, steps, natural=True)
     assert torch.isfinite(t_g).all() and torch.isfinite(U_g).all()
     assert torch.equal(t_g, f), (t_g, f)
     assert torch.equal(U_g, U)

@@ -89,8 +89,8 @@ def test_fused_run_equals_partial_finish_loop_bitwise(N, d, K):
     over 8 workgroups of 16 columns, including concept width 64 and heavily padded d = 66 / 72).
     Its trajectory and U must equal, bit for bit, the explicit loop of the partial and the
     one-workgroup finish entry points."""
-    from drsa_audio_amd import _capi
-    from drsa_audio_amd.xai.drsa.drsa import DrsaWorkspace, drsa_run
+    from drsa_slab_ref import explicit_loop
+    from drsa_audio_amd.xai.drsa.drsa import drsa_run
     steps = 6
     A, C = drsa_inputs(N, d, 31)
     Ag, Cg, Ug = _gpu(A, C, _u0(d, 8))
@@ -98,20 +98,7 @@ def test_fused_run_equals_partial_finish_loop_bitwise(N, d, K):
     with torch.cuda.stream(side):
         U_run, traj = drsa_run(Ag, Cg, Ug, K, steps)
     torch.cuda.synchronize()
-    ws = DrsaWorkspace(N, d, K, DEV)
-    st = _capi.stream_ptr()
-    gs = ws.gs
-    f = torch.empty(steps + 1, device=DEV)
-    U = Ug.clone()
-    for t in range(steps + 1):
-        _capi.call("drsa_amd_drsa_partial", Ag.data_ptr(), Cg.data_ptr(), N, d, K, U.data_ptr(), gs.data_ptr(),
-                   ws.ptr, ws.nbytes, st)
-        U_new = torch.empty_like(U)
-        _capi.call("drsa_amd_drsa_finish", gs.data_ptr(), N, d, K, U.data_ptr(), U_new.data_ptr(),
-                   f[t:].data_ptr(), 1 if t == steps else 0, None, st)
-        if t < steps:
-            U = U_new
-    torch.cuda.synchronize()
+    f, U = explicit_loop(Ag, Cg, Ug, K, steps)
     assert torch.equal(torch.as_tensor(traj).to(f), f), (traj, f)
     assert torch.equal(U_run, U)
 
