@@ -13,8 +13,10 @@
 // drsa_amd_istft_envelope is host code: the window's overlap-added sum of squares over the kept
 // span (a plan constant) and the check that it is invertible.
 //
-// The FFTs are the log-mel front end's wave-local Stockham passes (stockham.h); the inverse
-// n_fft-point real transform is an n_fft/2-point complex one run as conj(DFT(conj z)).
+// The transforms, forward and inverse, are the wave-local ones of stockham.h.  The argument checks
+// and the synthesis's spans, frames and overlap-add are audio_synth.h's, shared with stft_audio.hip:
+// mel_to_audio_kernel keeps what is its own, the mel tile, the P m contraction and Y = mag x phase.
+#include "audio_synth.h"
 #include "common.h"
 #include "drsa_amd.h"
 #include "stockham.h"
@@ -27,25 +29,8 @@ namespace {
 constexpr int AG_WAVES = 8;
 constexpr int AG_THREADS = AG_WAVES * 64;
 constexpr int AG_TF = 16;               // frames per workgroup (= the MFMA tile's 16 columns)
-// the synthesis kernel: one wave per frame of the tile
-constexpr int SY_WAVES = AG_TF;
-constexpr int SY_THREADS = SY_WAVES * 64;
 constexpr int AG_PB = 16;               // blocks of 4 rows of P^T a lane loads ahead of its MFMAs
-constexpr size_t AG_LDS_MAX = 160 * 1024;
-
-// twiddle tables from exact fp64 angles rounded once to fp32 (as logmel.hip)
-__device__ __forceinline__ void fill_twiddles(cf* tw, cf* ptw, int M, int tid, int nthreads) {
-  for (int j = tid; j < M; j += nthreads) {
-    double s, c;
-    sincospi(2.0 * (double)j / (double)M, &s, &c);
-    tw[j] = {(float)c, (float)-s};                    // W_M^j
-  }
-  for (int k = tid; k <= M; k += nthreads) {
-    double s, c;
-    sincospi((double)k / (double)M, &s, &c);
-    ptw[k] = {(float)c, (float)-s};                   // W_N^k, N = 2M
-  }
-}
+static_assert(SY_TF == AG_TF, "the synthesis runs one wave per column of the MFMA tile");
 
 // ===========================================================================
 // Analysis: one workgroup per (chunk, block of 16 frames), one frame per wave at a time.
@@ -112,26 +97,15 @@ __global__ __launch_bounds__(AG_THREADS) void stft_mel_phase_kernel(StftArgs a) 
     if (t >= a.width) break;
     const int base = (a.frame0 + t) * a.hop - half;
     for (int n = lane; n < M; n += 64) {
-      int j0 = base + 2 * n, j1 = j0 + 1;
-      j0 = j0 < 0 ? -j0 : j0;                          // reflect (torch pad_mode="reflect")
-      j0 = j0 >= a.L ? 2 * (a.L - 1) - j0 : j0;
-      j1 = j1 < 0 ? -j1 : j1;
-      j1 = j1 >= a.L ? 2 * (a.L - 1) - j1 : j1;
-      fa[n] = {(x[j0] / pk) * win[2 * n], (x[j1] / pk) * win[2 * n + 1]};
+      const int j = base + 2 * n;
+      fa[n] = {(x[reflect_index(j, a.L)] / pk) * win[2 * n], (x[reflect_index(j + 1, a.L)] / pk) * win[2 * n + 1]};
     }
     wave_lds_sync();
     cf* src = stockham_fft(fa, fb, tw, M, a.n_stages, a.radix, lane);
     float* mag = reinterpret_cast<float*>(src == fa ? fb : fa);
-    // real-input split: X[k] = E[k] + W_N^k O[k], E = (Z_k + conj Z_{M-k})/2, O = (Z_k - conj Z_{M-k})/(2i)
     float2* Xo = reinterpret_cast<float2*>(a.X) + ((int64_t)chunk * a.width + t) * nfreq;
     for (int k = lane; k <= M; k += 64) {
-      const cf zk = src[k == M ? 0 : k];
-      const cf zr = src[k == 0 ? 0 : M - k];
-      const cf zc = {zr.x, -zr.y};
-      const cf e = cscale(cadd(zk, zc), 0.5f);
-      const cf d = csub(zk, zc);
-      const cf o = {0.5f * d.y, -0.5f * d.x};
-      const cf X = cadd(e, cmul(ptw[k], o));
+      const cf X = real_split(src, ptw, k, M);
       Xo[k] = make_float2(X.x, X.y);
       const float p2 = X.x * X.x + X.y * X.y;
       mag[k] = a.power == 2 ? p2 : sqrtf(p2);
@@ -218,17 +192,9 @@ __global__ __launch_bounds__(AG_THREADS) void heatmap_mask_kernel(MaskArgs a) {
     const int y = i / a.W, xx = i % a.W;
     float acc = 0.f;
     for (int dy = 0; dy < a.k; ++dy) {
-      int yy = y + dy - r;
-      yy = yy < 0 ? -yy : yy;
-      yy = yy >= a.H ? 2 * (a.H - 1) - yy : yy;
-      const float* row = v + yy * a.W;
+      const float* row = v + reflect_index(y + dy - r, a.H) * a.W;
       float s = 0.f;
-      for (int dx = 0; dx < a.k; ++dx) {
-        int xc = xx + dx - r;
-        xc = xc < 0 ? -xc : xc;
-        xc = xc >= a.W ? 2 * (a.W - 1) - xc : xc;
-        s = fmaf(taps[dx], row[xc], s);
-      }
+      for (int dx = 0; dx < a.k; ++dx) s = fmaf(taps[dx], row[reflect_index(xx + dx - r, a.W)], s);
       acc = fmaf(taps[dy], s, acc);
     }
     o[i] = acc;
@@ -236,77 +202,54 @@ __global__ __launch_bounds__(AG_THREADS) void heatmap_mask_kernel(MaskArgs a) {
 }
 
 // ===========================================================================
-// Synthesis: one workgroup per (source, span of G hops of padded output positions).  It computes
-// the AG_TF = G + extra frames that touch its span, for each of the source's C masks in turn:
+// Synthesis: audio_synth.h's spans (one workgroup per (source, span), one wave per frame of the
+// AG_TF-frame tile) with the frames' bins from the masked mel, for each of the source's C masks:
 //   m[j][t]   = mel[j][t] * mask_c[j][t]                         (LDS, the mel tile is loaded once)
 //   mag[t][f] = relu(sum_j P[f][j] m[j][t])^(1/power)            (fp32 MFMA 16x16x4: 16 bins x 16 frames,
 //                                                                 two k-ordered fma chains over j)
-//   Y = mag * X / |X|  ->  n_fft-point inverse real FFT  ->  * window / n_fft   (wave w = frame w of the tile;
-//                                                                 the windowed frame goes to the wave's free
-//                                                                 ping-pong buffer)
-//   out[p] = (sum over the frames t that cover p, ascending t) / envelope[p]
-// Each output sample is written by exactly one workgroup with a fixed summation order.
+//   Y = mag * X / |X|  ->  synth_frame  ->  overlap_add_span
 // ===========================================================================
 struct SynArgs {
+  SynGeom g;
   const float* mel;          // [n][n_mels][width]
-  const float* X;            // [n][width][n_freq] complex
   const float* mask;         // [n][C][n_mels][width]
-  const float* window;       // [nfft]
   const float* pinv_t;       // [n_mels][n_freq]: P transposed
-  const float* wss;          // [outlen] window envelope over the kept span
-  float* out;                // [n][C][outlen]
-  int C, nfft, hop, n_mels, width, power;
-  int n_stages;
-  int radix[LM_MAX_STAGES];
-  int G, extra, nspan, outlen;
+  int n_mels, power;
   int njb;                   // blocks of 4 mel rows, even (zero rows pad the m tile)
   int FS;                    // mag row stride: n_freq rounded up to 16
-  int o_tw, o_ptw, o_win, o_melt, o_m, o_mag, o_fft;
+  int o_melt, o_m, o_mag;
 };
 
 __global__ __launch_bounds__(SY_THREADS) void mel_to_audio_kernel(SynArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
-  const int64_t b = blockIdx.x / a.nspan;
-  const int g = blockIdx.x % a.nspan;
-  const int M = a.nfft >> 1, half = a.nfft >> 1, nfreq = M + 1;
-  const int t0 = g * a.G - a.extra;                    // first frame of the tile (may be < 0)
-  cf* tw = reinterpret_cast<cf*>(sm + a.o_tw);
-  cf* ptw = reinterpret_cast<cf*>(sm + a.o_ptw);
-  float* win = sm + a.o_win;
+  const SynSpan s = synth_span(a.g, sm);
+  const int64_t b = s.b;
+  const int t0 = s.t0, width = a.g.width;
+  const int M = a.g.nfft >> 1, nfreq = M + 1;
   float* melt = sm + a.o_melt;                         // [4 njb][AG_TF]
   float* mt = sm + a.o_m;                              // [4 njb][AG_TF]
   float* mag = sm + a.o_mag;                           // [AG_TF][FS]
-  cf* fa = reinterpret_cast<cf*>(sm + a.o_fft) + (size_t)w * 2 * M;
-  cf* fb = fa + M;
-  // the transform of an even number of passes ends in fa, so the windowed frame (n_fft floats = one
-  // buffer) goes to fb, and the other way round: frame tl of the tile is at fr + tl * 2 n_fft
-  float* fr = sm + a.o_fft + ((a.n_stages & 1) ? 0 : 2 * M);
-  const float invN = 1.f / (float)a.nfft;
 
-  fill_twiddles(tw, ptw, M, tid, SY_THREADS);
-  for (int i = tid; i < a.nfft; i += SY_THREADS) win[i] = a.window[i];
+  synth_fill_tables(a.g, s, tid);
   const int ntile = a.njb * 4 * AG_TF;
   for (int i = tid; i < ntile; i += SY_THREADS) {
     const int j = i / AG_TF, t = t0 + i % AG_TF;
-    const bool ok = j < a.n_mels && t >= 0 && t < a.width;
-    melt[i] = ok ? a.mel[(b * a.n_mels + j) * a.width + t] : 0.f;
+    const bool ok = j < a.n_mels && t >= 0 && t < width;
+    melt[i] = ok ? a.mel[(b * a.n_mels + j) * width + t] : 0.f;
   }
-  const int p_lo = max(g * a.G * a.hop, half);
-  const int p_hi = min((g + 1) * a.G * a.hop, half + a.outlen);
 
-  for (int c = 0; c < a.C; ++c) {
-    const float* mask = a.mask + (b * a.C + c) * (int64_t)a.n_mels * a.width;
-    float* out = a.out + (b * a.C + c) * (int64_t)a.outlen;
+  for (int c = 0; c < a.g.C; ++c) {
+    const float* mask = a.mask + (b * a.g.C + c) * (int64_t)a.n_mels * width;
     __syncthreads();                                   // tables + mel tile ready / previous audio done
     for (int i = tid; i < ntile; i += SY_THREADS) {
       const int j = i / AG_TF, t = t0 + i % AG_TF;
-      const bool ok = j < a.n_mels && t >= 0 && t < a.width;
-      mt[i] = ok ? melt[i] * mask[(int64_t)j * a.width + t] : 0.f;
+      const bool ok = j < a.n_mels && t >= 0 && t < width;
+      mt[i] = ok ? melt[i] * mask[(int64_t)j * width + t] : 0.f;
     }
     __syncthreads();
     // ---- mag = relu(P m)^(1/power): wave w takes the 16-bin tiles w, w + 8, ... ----
-    for (int f0 = w * 16; f0 < nfreq; f0 += SY_WAVES * 16) {
+    for (int f0 = w * 16; f0 < nfreq; f0 += SY_TF * 16) {
       const int fi = min(f0 + (lane & 15), nfreq - 1);
       const int kq = lane >> 4;
       f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -336,10 +279,10 @@ __global__ __launch_bounds__(SY_THREADS) void mel_to_audio_kernel(SynArgs a) {
     }
     __syncthreads();
     // ---- wave w: spectrum of frame t0 + w -> windowed time frame ----
-    if (const int tl = w, t = t0 + w; t >= 0 && t < a.width) {
-      const float2* Xp = reinterpret_cast<const float2*>(a.X) + (b * a.width + t) * nfreq;
+    if (const int tl = w, t = t0 + w; t >= 0 && t < width) {
+      const float2* Xp = reinterpret_cast<const float2*>(a.g.X) + (b * width + t) * nfreq;
       const float* mg = mag + tl * a.FS;
-      auto Y = [&](int k) -> cf {
+      synth_frame(a.g, s, tl, [&](int k) -> cf {
         const float2 X = Xp[k];
         const float n2 = X.x * X.x + X.y * X.y;
         cf ph = {1.f, 0.f};                            // librosa magphase: 1 + 0i where |X| = 0
@@ -347,38 +290,11 @@ __global__ __launch_bounds__(SY_THREADS) void mel_to_audio_kernel(SynArgs a) {
           const float inv = 1.f / sqrtf(n2);
           ph = {X.x * inv, X.y * inv};
         }
-        cf y = cscale(ph, mg[k]);
-        if (k == 0 || k == M) y.y = 0.f;               // a real signal's DC and Nyquist bins (irfft ignores them)
-        return y;
-      };
-      // half-length packing: z[n] = x[2n] + i x[2n+1] = IDFT_M(Z)/2,
-      //   Z[k] = (Y[k] + conj Y[M-k]) + i (Y[k] - conj Y[M-k]) conj(W_N^k);   IDFT = conj DFT conj
-      for (int k = lane; k < M; k += 64) {
-        const cf yk = Y(k), ym = Y(M - k);
-        const cf yc = {ym.x, -ym.y};
-        const cf e = cadd(yk, yc);
-        const cf o = cmul(csub(yk, yc), cf{ptw[k].x, -ptw[k].y});
-        fa[k] = {e.x - o.y, -(e.y + o.x)};
-      }
-      wave_lds_sync();
-      const cf* F = stockham_fft(fa, fb, tw, M, a.n_stages, a.radix, lane);
-      float* fo = fr + tl * 2 * a.nfft;                // this wave's buffer that does not hold F
-      for (int n = lane; n < M; n += 64) {
-        fo[2 * n] = (F[n].x * invN) * win[2 * n];
-        fo[2 * n + 1] = (-F[n].y * invN) * win[2 * n + 1];
-      }
+        return cscale(ph, mg[k]);
+      }, lane);
     }
     __syncthreads();
-    // ---- owned overlap-add over this workgroup's span ----
-    for (int p = p_lo + tid; p < p_hi; p += SY_THREADS) {
-      float acc = 0.f;
-      const int t_hi = p / a.hop;                      // the last frame that starts at or before p
-      for (int t = t_hi - a.extra; t <= t_hi; ++t) {   // ascending t: the fixed summation order
-        const int off = p - t * a.hop;
-        if (t >= 0 && t < a.width && off < a.nfft) acc += fr[(t - t0) * 2 * a.nfft + off];
-      }
-      out[p - half] = acc / a.wss[p - half];
-    }
+    overlap_add_span(a.g, s, c, tid);
   }
 }
 
@@ -438,18 +354,6 @@ __global__ __launch_bounds__(AN_THREADS) void audio_normalize_kernel(float* audi
   }
 }
 
-// common shape rules of the transforms
-int check_fft_shape(const char* who, int n_fft, int hop, int n_mels, int width, int power, int* radix,
-                    int* n_stages) {
-  DRSA_REQUIRE(n_fft >= 8 && n_fft % 2 == 0, "%s: n_fft must be even and >= 8 (got %d)", who, n_fft);
-  DRSA_REQUIRE(hop >= 1 && n_mels >= 1 && width >= 1, "%s: bad hop/n_mels/width", who);
-  DRSA_REQUIRE(hop <= n_fft, "%s: hop %d > n_fft %d leaves gaps between frames", who, hop, n_fft);
-  DRSA_REQUIRE(power == 1 || power == 2, "%s: power must be 1 or 2 (got %d)", who, power);
-  *n_stages = factor_radices(n_fft / 2, radix);
-  DRSA_REQUIRE(*n_stages > 0, "%s: n_fft/2 = %d must factor into 2, 3, 5", who, n_fft / 2);
-  return DRSA_OK;
-}
-
 }  // namespace
 
 extern "C" int drsa_amd_stft_mel_phase(const float* wav, int64_t n_chunks, int64_t chunk_stride, int chunk_len,
@@ -461,6 +365,7 @@ extern "C" int drsa_amd_stft_mel_phase(const float* wav, int64_t n_chunks, int64
                "stft_mel_phase: null pointer");
   StftArgs a{};
   if (int rc = check_fft_shape("stft_mel_phase", n_fft, hop, n_mels, width, power, a.radix, &a.n_stages)) return rc;
+  DRSA_REQUIRE(aligned8(X), "stft_mel_phase: X is written as (re, im) pairs and must be 8-byte aligned");
   DRSA_REQUIRE(n_chunks >= 0 && frame0 >= 0 && band_nnz >= 0, "stft_mel_phase: bad n_chunks/frame0/band_nnz");
   DRSA_REQUIRE(chunk_len > n_fft / 2, "stft_mel_phase: reflect padding needs chunk_len > n_fft/2");
   DRSA_REQUIRE(frame0 + width <= 1 + chunk_len / hop, "stft_mel_phase: frames %d..%d exceed the %d STFT frames",
@@ -488,20 +393,19 @@ extern "C" int drsa_amd_stft_mel_phase(const float* wav, int64_t n_chunks, int64
   a.mel = mel;
   a.X = X;
   const int M = n_fft / 2;
-  int off = 0;
-  auto take = [&](int n) { int o = off; off += (n + 3) & ~3; return o; };
-  a.o_tw = take(2 * M);
-  a.o_ptw = take(2 * (M + 1));
-  a.o_win = take(n_fft);
-  a.o_blo = take(n_mels);
-  a.o_bn = take(n_mels);
-  a.o_boff = take(n_mels);
-  a.o_bw = take(band_nnz);
-  a.o_fft = take(AG_WAVES * 4 * M);
-  a.o_mel = take(n_mels * AG_TF);
-  a.o_red = take(AG_WAVES);
-  const size_t smem = (size_t)off * 4;
-  if (smem > AG_LDS_MAX) {
+  LdsCarve lds;
+  a.o_tw = lds.take(2 * M);
+  a.o_ptw = lds.take(2 * (M + 1));
+  a.o_win = lds.take(n_fft);
+  a.o_blo = lds.take(n_mels);
+  a.o_bn = lds.take(n_mels);
+  a.o_boff = lds.take(n_mels);
+  a.o_bw = lds.take(band_nnz);
+  a.o_fft = lds.take(AG_WAVES * 4 * M);
+  a.o_mel = lds.take(n_mels * AG_TF);
+  a.o_red = lds.take(AG_WAVES);
+  const size_t smem = lds.bytes();
+  if (smem > DRSA_LDS_MAX) {
     drsa::set_error("stft_mel_phase: LDS footprint %zu B exceeds 160 KB (n_fft %d, n_mels %d)", smem, n_fft, n_mels);
     return DRSA_EUNSUPPORTED;
   }
@@ -514,16 +418,11 @@ extern "C" int drsa_amd_stft_mel_phase(const float* wav, int64_t n_chunks, int64
 
 extern "C" int drsa_amd_heatmap_mask(const float* heatmaps, int64_t n_maps, int H, int W, int group, int rank_first,
                                      int rank_rest, const float* taps, int k, float* mask, void* stream) {
-  DRSA_REQUIRE(heatmaps && taps && mask, "heatmap_mask: null pointer");
-  DRSA_REQUIRE(n_maps >= 0 && n_maps < (1LL << 31) && H >= 1 && W >= 1 && group >= 1,
-               "heatmap_mask: bad n_maps/H/W/group");
-  DRSA_REQUIRE(k >= 1 && k % 2 == 1 && k <= 63, "heatmap_mask: blur kernel size must be odd and in [1, 63] (got %d)", k);
-  DRSA_REQUIRE(k / 2 < H && k / 2 < W, "heatmap_mask: reflect padding %d needs a larger map than %dx%d", k / 2, H, W);
+  if (int rc = check_mask_args("heatmap_mask", heatmaps, n_maps, H, W, group, rank_first, rank_rest, taps, k, mask))
+    return rc;
   const int64_t n = (int64_t)H * W;
-  DRSA_REQUIRE(rank_first >= -1 && rank_first < n && rank_rest >= -1 && rank_rest < n,
-               "heatmap_mask: rank must be -1 (no threshold) or in [0, H*W)");
   const size_t smem = ((size_t)((n + 3) & ~3) + ((k + 3) & ~3) + 256) * 4;
-  if (smem > AG_LDS_MAX) {
+  if (smem > DRSA_LDS_MAX) {
     drsa::set_error("heatmap_mask: a %dx%d map (%zu B with its tables) does not fit the 160 KB LDS", H, W, smem);
     return DRSA_EUNSUPPORTED;
   }
@@ -565,53 +464,29 @@ extern "C" int drsa_amd_mel_to_audio(const float* mel, const float* X, const flo
                                      const float* pinv_t, const float* envelope, float* audio, void* stream) {
   DRSA_REQUIRE(mel && X && mask && window && pinv_t && envelope && audio, "mel_to_audio: null pointer");
   SynArgs a{};
-  if (int rc = check_fft_shape("mel_to_audio", n_fft, hop, n_mels, width, power, a.radix, &a.n_stages)) return rc;
-  DRSA_REQUIRE(n_src >= 0 && C >= 1 && width >= 2, "mel_to_audio: need n_src >= 0, C >= 1, width >= 2");
-  const int extra = (n_fft + hop - 1) / hop - 1;       // earlier frames that reach into a span
-  if (extra > AG_TF / 2) {
-    drsa::set_error("mel_to_audio: n_fft/hop = %d/%d overlaps more than %d frames", n_fft, hop, AG_TF / 2 + 1);
-    return DRSA_EUNSUPPORTED;
-  }
-  const int M = n_fft / 2, nfreq = M + 1;
+  LdsCarve lds;
+  if (int rc = synth_plan("mel_to_audio", a.g, lds, X, n_src, C, n_fft, hop, n_mels, width, power, window, envelope,
+                          audio))
+    return rc;
   a.mel = mel;
-  a.X = X;
   a.mask = mask;
-  a.window = window;
   a.pinv_t = pinv_t;
-  a.wss = envelope;
-  a.out = audio;
-  a.C = C;
-  a.nfft = n_fft;
-  a.hop = hop;
   a.n_mels = n_mels;
-  a.width = width;
   a.power = power;
-  a.extra = extra;
-  a.G = AG_TF - extra;
-  const int64_t outlen = (int64_t)hop * (width - 1);
-  DRSA_REQUIRE(outlen + n_fft < (1LL << 30), "mel_to_audio: audio too long");
-  a.outlen = (int)outlen;
-  a.nspan = (int)((M + outlen + (int64_t)a.G * hop - 1) / ((int64_t)a.G * hop));
-  DRSA_REQUIRE(n_src * a.nspan < (1LL << 31), "mel_to_audio: too many sources");
   a.njb = 2 * ((n_mels + 7) / 8);
-  a.FS = 16 * ((nfreq + 15) / 16);
-  int off = 0;
-  auto take = [&](int n) { int o = off; off += (n + 3) & ~3; return o; };
-  a.o_tw = take(2 * M);
-  a.o_ptw = take(2 * (M + 1));
-  a.o_win = take(n_fft);
-  a.o_melt = take(a.njb * 4 * AG_TF);
-  a.o_m = take(a.njb * 4 * AG_TF);
-  a.o_mag = take(AG_TF * a.FS);
-  a.o_fft = take(SY_WAVES * 4 * M);
-  const size_t smem = (size_t)off * 4;
-  if (smem > AG_LDS_MAX) {
+  a.FS = 16 * ((n_fft / 2 + 1 + 15) / 16);
+  a.o_melt = lds.take(a.njb * 4 * AG_TF);
+  a.o_m = lds.take(a.njb * 4 * AG_TF);
+  a.o_mag = lds.take(AG_TF * a.FS);
+  synth_take_fft(a.g, lds);
+  const size_t smem = lds.bytes();
+  if (smem > DRSA_LDS_MAX) {
     drsa::set_error("mel_to_audio: LDS footprint %zu B exceeds 160 KB (n_fft %d, n_mels %d)", smem, n_fft, n_mels);
     return DRSA_EUNSUPPORTED;
   }
   if (n_src == 0) return DRSA_OK;
   DRSA_SMEM(mel_to_audio_kernel, smem);
-  hipLaunchKernelGGL(mel_to_audio_kernel, dim3((unsigned)(n_src * a.nspan)), dim3(SY_THREADS), smem,
+  hipLaunchKernelGGL(mel_to_audio_kernel, dim3((unsigned)(n_src * a.g.nspan)), dim3(SY_THREADS), smem,
                      (hipStream_t)stream, a);
   DRSA_LAUNCH_CHECK();
   return DRSA_OK;

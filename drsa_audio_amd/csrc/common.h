@@ -53,6 +53,23 @@ int cu_count();
 #define DRSA_LAUNCH_CHECK() DRSA_HIP(hipGetLastError())
 
 // ---------------------------------------------------------------------------
+// dynamic LDS: the limit of one workgroup and the host-side carve of a kernel's buffers
+// ---------------------------------------------------------------------------
+constexpr size_t DRSA_LDS_MAX = 160 * 1024;
+
+// Offsets in floats, every buffer rounded up to 4 floats (16-byte aligned).  The sum is kept in 64
+// bits so that a footprint far past the limit is refused and does not wrap.
+struct LdsCarve {
+  int64_t off = 0;
+  int take(int64_t n) {
+    const int64_t o = off;
+    off += (n + 3) & ~3LL;
+    return (int)o;
+  }
+  size_t bytes() const { return (size_t)off * 4; }
+};
+
+// ---------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------
 // fp32-input MFMA, 16x16x4 (exact f32 fma chain, k-ordered).

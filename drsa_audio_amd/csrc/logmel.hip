@@ -8,12 +8,14 @@
 // One workgroup per audio chunk, 8 waves.  The chunk's samples stream through LDS in blocks of
 // 8 frames (one frame per wave, reflect padding resolved on the load); each wave runs the
 // n_fft-point real FFT as an n_fft/2-point complex Stockham FFT (radices 4/2/3/5) in its own
-// LDS ping-pong buffers, the real-input split, |X|, and the sparse triangular mel filterbank
+// LDS ping-pong buffers, the real-input split (tables, transform and split are stockham.h's,
+// shared with the concept-audio kernels), |X|, and the sparse triangular mel filterbank
 // (each filter is a contiguous band of FFT bins).  Mel columns collect in LDS so the
 // [n_mels][width] output leaves as coalesced rows.  The STFT and the filterbank are
 // linear and |.| is positively homogeneous, so the per-chunk peak division is applied to the
 // mel energies at the end: one read of the waveform (HBM roofline: 4*(L + n_mels*width) B per
-// chunk).
+// chunk).  logmel800_kernel (below) is the n_fft = 800 fast path with its own tables and transform;
+// both kernels take their LDS layout from logmel_carve.
 #include "common.h"
 #include "drsa_amd.h"
 #include "stockham.h"
@@ -69,17 +71,8 @@ __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(LogmelArgs a) {
   float* mel = sm + a.o_mel;
   float* red = sm + a.o_red;
 
-  // ---- tables (twiddles from exact fp64 angles rounded once to fp32) ----
-  for (int j = tid; j < M; j += LM_THREADS) {
-    double s, c;
-    sincospi(2.0 * (double)j / (double)M, &s, &c);
-    tw[j] = {(float)c, (float)-s};
-  }
-  for (int k = tid; k <= M; k += LM_THREADS) {
-    double s, c;
-    sincospi((double)k / (double)M, &s, &c);          // 2*pi*k/N, N = 2M
-    ptw[k] = {(float)c, (float)-s};
-  }
+  // ---- tables ----
+  fill_twiddles(tw, ptw, M, tid, LM_THREADS);
   for (int i = tid; i < a.nfft; i += LM_THREADS) win[i] = a.window[i];
   for (int m = tid; m < a.n_mels; m += LM_THREADS) {
     blo[m] = a.band_lo[m];
@@ -96,10 +89,7 @@ __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(LogmelArgs a) {
     const int cnt = (nw - 1) * a.hop + a.nfft;
     __syncthreads();   // previous block's frames are done with samp (and the tables are ready)
     for (int i = tid; i < cnt; i += LM_THREADS) {
-      int j = base + i;
-      j = j < 0 ? -j : j;                                  // reflect (torch pad_mode="reflect")
-      j = j >= a.L ? 2 * (a.L - 1) - j : j;
-      const float v = x[j];
+      const float v = x[reflect_index(base + i, a.L)];
       samp[i] = v;
       pk = fmaxf(pk, fabsf(v));
     }
@@ -109,31 +99,10 @@ __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(LogmelArgs a) {
       // pack the windowed real frame as M complex points z[n] = x[2n] + i x[2n+1]
       for (int n = lane; n < M; n += 64) fa[n] = {fr[2 * n] * win[2 * n], fr[2 * n + 1] * win[2 * n + 1]};
       wave_lds_sync();
-      cf* src = fa;
-      cf* dst = fb;
-      int Ns = 1;
-      for (int s = 0; s < a.n_stages; ++s) {
-        const int R = a.radix[s];
-        if (R == 4) stockham_pass<4>(src, dst, tw, M, Ns, lane);
-        else if (R == 5) stockham_pass<5>(src, dst, tw, M, Ns, lane);
-        else if (R == 3) stockham_pass<3>(src, dst, tw, M, Ns, lane);
-        else stockham_pass<2>(src, dst, tw, M, Ns, lane);
-        wave_lds_sync();
-        Ns *= R;
-        cf* t = src;
-        src = dst;
-        dst = t;
-      }
-      // real-input split: X[k] = E[k] + W_N^k O[k], E = (Z_k + conj Z_{M-k})/2, O = (Z_k - conj Z_{M-k})/(2i)
-      float* mag = reinterpret_cast<float*>(dst);
+      const cf* Z = stockham_fft(fa, fb, tw, M, a.n_stages, a.radix, lane);
+      float* mag = reinterpret_cast<float*>(Z == fa ? fb : fa);
       for (int k = lane; k <= M; k += 64) {
-        const cf zk = src[k == M ? 0 : k];
-        const cf zr = src[k == 0 ? 0 : M - k];
-        const cf zc = {zr.x, -zr.y};
-        const cf e = cscale(cadd(zk, zc), 0.5f);
-        const cf d = csub(zk, zc);
-        const cf o = {0.5f * d.y, -0.5f * d.x};
-        const cf X = cadd(e, cmul(ptw[k], o));
+        const cf X = real_split(Z, ptw, k, M);
         mag[k] = sqrtf(X.x * X.x + X.y * X.y);
       }
       wave_lds_sync();
@@ -509,6 +478,25 @@ __global__ __launch_bounds__(LF_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
 #endif
 }
 
+// The LDS layout of logmel_kernel, or of logmel800_kernel (fast), into a.o_*; returns its bytes.
+size_t logmel_carve(LogmelArgs& a, bool fast, int n_fft, int hop, int n_mels, int width, int band_nnz) {
+  const int M = n_fft / 2;
+  LdsCarve lds;
+  a.o_tw = lds.take(2 * M);
+  a.o_ptw = lds.take(2 * (M + 1));
+  a.o_win = lds.take(n_fft);
+  a.o_blo = lds.take(n_mels);
+  a.o_bn = lds.take(n_mels);
+  a.o_boff = lds.take(n_mels);
+  a.o_bw = lds.take(band_nnz);
+  a.o_samp = lds.take(fast ? 0 : (LM_WAVES - 1) * hop + n_fft);
+  a.o_fft = lds.take(fast ? LF_WAVES * LF_WB : LM_WAVES * 4 * M);
+  a.o_mel = lds.take(fast ? 0 : n_mels * width);
+  a.o_bwt = lds.take(fast ? LF_NBT * (n_mels + 1) : 0);
+  a.o_red = lds.take(fast ? LF_WAVES : LM_WAVES);
+  a.smem_floats = (int)(lds.bytes() / 4);
+  return lds.bytes();
+}
 
 }  // namespace
 
@@ -518,21 +506,8 @@ extern "C" int drsa_amd_logmel_prof(unsigned long long* host, int n) {
 }
 #endif
 extern "C" int drsa_amd_logmel_smem_bytes(int n_fft, int hop, int n_mels, int width, int band_nnz) {
-  const int M = n_fft / 2;
-  int off = 0;
-  auto take = [&](int n) { int o = off; off += (n + 3) & ~3; return o; };
-  take(2 * M);
-  take(2 * (M + 1));
-  take(n_fft);
-  take(n_mels);
-  take(n_mels);
-  take(n_mels);
-  take(band_nnz);
-  take((LM_WAVES - 1) * hop + n_fft);
-  take(LM_WAVES * 4 * M);
-  take(n_mels * width);
-  take(LM_WAVES);
-  return off * 4;
+  LogmelArgs a{};
+  return (int)logmel_carve(a, false, n_fft, hop, n_mels, width, band_nnz);
 }
 
 extern "C" int drsa_amd_logmel(const float* wav, int64_t n_songs, int64_t song_stride, int chunks_per_song,
@@ -576,29 +551,10 @@ extern "C" int drsa_amd_logmel(const float* wav, int64_t n_songs, int64_t song_s
   a.clamp_min = clamp_min;
   a.log_eps = log_eps;
   a.out = out;
-  const int M = n_fft / 2;
-  auto carve = [&](bool fast) {
-    int off = 0;
-    auto take = [&](int n) { int o = off; off += (n + 3) & ~3; return o; };
-    a.o_tw = take(2 * M);
-    a.o_ptw = take(2 * (M + 1));
-    a.o_win = take(n_fft);
-    a.o_blo = take(n_mels);
-    a.o_bn = take(n_mels);
-    a.o_boff = take(n_mels);
-    a.o_bw = take(band_nnz);
-    a.o_samp = take(fast ? 0 : (LM_WAVES - 1) * hop + n_fft);
-    a.o_fft = take(fast ? LF_WAVES * LF_WB : LM_WAVES * 4 * M);
-    a.o_mel = take(fast ? 0 : n_mels * width);
-    a.o_bwt = take(fast ? LF_NBT * (n_mels + 1) : 0);
-    a.o_red = take(fast ? LF_WAVES : LM_WAVES);
-    a.smem_floats = off;
-    return (size_t)off * 4;
-  };
-  // the 16-wave n_fft = 800 kernel when its tables + mel tile fit in LDS, else the generic kernel
-  bool fast = n_fft == 800 && carve(true) <= 160 * 1024;
-  const size_t smem = carve(fast);
-  DRSA_REQUIRE(smem <= 160 * 1024, "logmel: LDS footprint %zu B exceeds 160 KB (n_mels*width too large)", smem);
+  // the n_fft = 800 kernel when its tables fit in LDS, else the generic kernel
+  const bool fast = n_fft == 800 && logmel_carve(a, true, n_fft, hop, n_mels, width, band_nnz) <= DRSA_LDS_MAX;
+  const size_t smem = logmel_carve(a, fast, n_fft, hop, n_mels, width, band_nnz);
+  DRSA_REQUIRE(smem <= DRSA_LDS_MAX, "logmel: LDS footprint %zu B exceeds 160 KB (n_mels*width too large)", smem);
   const void* fn = fast ? (const void*)logmel800_kernel : (const void*)logmel_kernel;
   DRSA_SMEM(fn, smem);
   if (fast)

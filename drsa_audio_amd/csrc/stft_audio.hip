@@ -8,11 +8,12 @@
 //   drsa_amd_heatmap_mask_large      drsa_amd_heatmap_mask for maps that do not fit the LDS: the map
 //                                    stays in global memory (L2), the blur runs on 64 x 64 tiles
 //   drsa_amd_stft_mask_to_audio      Y = mask x X -> inverse real FFT -> window -> owned overlap-add
-//                                    -> / window envelope -> trimmed audio (drsa_amd_mel_to_audio's
-//                                    second half; no mel tile, no pseudo-inverse)
+//                                    -> / window envelope -> trimmed audio (drsa_amd_mel_to_audio
+//                                    without the mel tile and the pseudo-inverse)
 //
-// audiogen.hip's kernels keep their code; the two small helpers both files need (the twiddle
-// tables, the transform's shape rules) are restated here.
+// The argument checks and everything of the synthesis after Y are audio_synth.h's, shared with
+// audiogen.hip; stft_mask_to_audio_kernel keeps the transposed mask tile and Y = mask x X.
+#include "audio_synth.h"
 #include "common.h"
 #include "drsa_amd.h"
 #include "stockham.h"
@@ -20,8 +21,6 @@
 #include <math.h>
 
 namespace {
-
-constexpr size_t SA_LDS_MAX = 160 * 1024;
 
 // ===========================================================================
 // Lift: one workgroup per (source, block of 32 frames), the source's C maps in turn.
@@ -133,11 +132,6 @@ struct MaskLargeArgs {
   int H, W, k, group, lo_first, lo_rest, split, tiles_x, ntiles;
 };
 
-__device__ __forceinline__ int reflect(int i, int n) {
-  i = i < 0 ? -i : i;
-  return i >= n ? 2 * (n - 1) - i : i;
-}
-
 __global__ __launch_bounds__(ML_THREADS) void heatmap_mask_large_kernel(MaskLargeArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x;
@@ -212,7 +206,7 @@ __global__ __launch_bounds__(ML_THREADS) void heatmap_mask_large_kernel(MaskLarg
 #pragma unroll
       for (int q = 0; q < ML_LOADS; ++q) {
         const int i = min(i0 + q * ML_THREADS, nh - 1);
-        x[q] = h[reflect(y0 - r + i / hw, a.H) * a.W + reflect(x0 - r + i % hw, a.W)];
+        x[q] = h[reflect_index(y0 - r + i / hw, a.H) * a.W + reflect_index(x0 - r + i % hw, a.W)];
       }
 #pragma unroll
       for (int q = 0; q < ML_LOADS; ++q) {
@@ -242,118 +236,51 @@ __global__ __launch_bounds__(ML_THREADS) void heatmap_mask_large_kernel(MaskLarg
 }
 
 // ===========================================================================
-// Synthesis: mel_to_audio_kernel's span ownership (one workgroup per (source, span of G hops of
-// padded output positions), the SY_TF = G + extra frames that touch the span, one wave per frame)
-// with the spectrum taken directly:
+// Synthesis: audio_synth.h's spans (one workgroup per (source, span), one wave per frame of the
+// SY_TF-frame tile) with the frames' bins taken from the spectrum directly:
 //   Y[t][f] = mask_c[f][t] * X[t][f]   (the mask tile is transposed through LDS)
-//   -> n_fft-point inverse real FFT -> * window / n_fft
-//   out[p] = (sum over the frames t that cover p, ascending t) / envelope[p]
-// Each output sample is written by exactly one workgroup with a fixed summation order.
+//   ->  synth_frame  ->  overlap_add_span
 // ===========================================================================
-constexpr int SY_TF = 16;               // frames per workgroup, one wave each
-constexpr int SY_THREADS = SY_TF * 64;
 constexpr int SY_MS = SY_TF + 1;        // row stride of the mask tile
 
-__device__ __forceinline__ void fill_twiddles(cf* tw, cf* ptw, int M, int tid, int nthreads) {
-  for (int j = tid; j < M; j += nthreads) {
-    double s, c;
-    sincospi(2.0 * (double)j / (double)M, &s, &c);
-    tw[j] = {(float)c, (float)-s};                    // W_M^j
-  }
-  for (int k = tid; k <= M; k += nthreads) {
-    double s, c;
-    sincospi((double)k / (double)M, &s, &c);
-    ptw[k] = {(float)c, (float)-s};                   // W_N^k, N = 2M
-  }
-}
-
 struct StftSynArgs {
-  const float* X;            // [n][width][n_freq] complex
+  SynGeom g;
   const float* mask;         // [n][C][n_freq][width]
-  const float* window;       // [nfft]
-  const float* wss;          // [outlen] window envelope over the kept span
-  float* out;                // [n][C][outlen]
-  int C, nfft, hop, width;
-  int n_stages;
-  int radix[LM_MAX_STAGES];
-  int G, extra, nspan, outlen;
-  int o_tw, o_ptw, o_win, o_mask, o_fft;
+  int o_mask;
 };
 
 __global__ __launch_bounds__(SY_THREADS) void stft_mask_to_audio_kernel(StftSynArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
-  const int64_t b = blockIdx.x / a.nspan;
-  const int g = blockIdx.x % a.nspan;
-  const int M = a.nfft >> 1, half = a.nfft >> 1, nfreq = M + 1;
-  const int t0 = g * a.G - a.extra;                    // first frame of the tile (may be < 0)
-  cf* tw = reinterpret_cast<cf*>(sm + a.o_tw);
-  cf* ptw = reinterpret_cast<cf*>(sm + a.o_ptw);
-  float* win = sm + a.o_win;
+  const SynSpan s = synth_span(a.g, sm);
+  const int64_t b = s.b;
+  const int t0 = s.t0, width = a.g.width;
+  const int M = a.g.nfft >> 1, nfreq = M + 1;
   float* mk = sm + a.o_mask;                           // [n_freq][SY_MS]
-  cf* fa = reinterpret_cast<cf*>(sm + a.o_fft) + (size_t)w * 2 * M;
-  cf* fb = fa + M;
-  // the transform of an even number of passes ends in fa, so the windowed frame (n_fft floats = one
-  // buffer) goes to fb, and the other way round: frame tl of the tile is at fr + tl * 2 n_fft
-  float* fr = sm + a.o_fft + ((a.n_stages & 1) ? 0 : 2 * M);
-  const float invN = 1.f / (float)a.nfft;
 
-  fill_twiddles(tw, ptw, M, tid, SY_THREADS);
-  for (int i = tid; i < a.nfft; i += SY_THREADS) win[i] = a.window[i];
-  const int p_lo = max(g * a.G * a.hop, half);
-  const int p_hi = min((g + 1) * a.G * a.hop, half + a.outlen);
+  synth_fill_tables(a.g, s, tid);
 
-  for (int c = 0; c < a.C; ++c) {
-    const float* mask = a.mask + (b * a.C + c) * (int64_t)nfreq * a.width;
-    float* out = a.out + (b * a.C + c) * (int64_t)a.outlen;
+  for (int c = 0; c < a.g.C; ++c) {
+    const float* mask = a.mask + (b * a.g.C + c) * (int64_t)nfreq * width;
     __syncthreads();                                   // tables ready / previous audio done
     for (int i = tid; i < nfreq * SY_TF; i += SY_THREADS) {
       const int f = i / SY_TF, tl = i % SY_TF, t = t0 + tl;
-      mk[f * SY_MS + tl] = (t >= 0 && t < a.width) ? mask[(int64_t)f * a.width + t] : 0.f;
+      mk[f * SY_MS + tl] = (t >= 0 && t < width) ? mask[(int64_t)f * width + t] : 0.f;
     }
     __syncthreads();
     // ---- wave w: masked spectrum of frame t0 + w -> windowed time frame ----
-    if (const int tl = w, t = t0 + w; t >= 0 && t < a.width) {
-      const float2* Xp = reinterpret_cast<const float2*>(a.X) + (b * a.width + t) * nfreq;
-      auto Y = [&](int k) -> cf {
+    if (const int tl = w, t = t0 + w; t >= 0 && t < width) {
+      const float2* Xp = reinterpret_cast<const float2*>(a.g.X) + (b * width + t) * nfreq;
+      synth_frame(a.g, s, tl, [&](int k) -> cf {
         const float2 X = Xp[k];
         const float m = mk[k * SY_MS + tl];
-        cf y = {m * X.x, m * X.y};
-        if (k == 0 || k == M) y.y = 0.f;               // a real signal's DC and Nyquist bins (irfft ignores them)
-        return y;
-      };
-      // half-length packing: z[n] = x[2n] + i x[2n+1] = IDFT_M(Z)/2,
-      //   Z[k] = (Y[k] + conj Y[M-k]) + i (Y[k] - conj Y[M-k]) conj(W_N^k);   IDFT = conj DFT conj
-      for (int k = lane; k < M; k += 64) {
-        const cf yk = Y(k), ym = Y(M - k);
-        const cf yc = {ym.x, -ym.y};
-        const cf e = cadd(yk, yc);
-        const cf o = cmul(csub(yk, yc), cf{ptw[k].x, -ptw[k].y});
-        fa[k] = {e.x - o.y, -(e.y + o.x)};
-      }
-      wave_lds_sync();
-      const cf* F = stockham_fft(fa, fb, tw, M, a.n_stages, a.radix, lane);
-      float* fo = fr + tl * 2 * a.nfft;                // this wave's buffer that does not hold F
-      for (int n = lane; n < M; n += 64) {
-        fo[2 * n] = (F[n].x * invN) * win[2 * n];
-        fo[2 * n + 1] = (-F[n].y * invN) * win[2 * n + 1];
-      }
+        return {m * X.x, m * X.y};
+      }, lane);
     }
     __syncthreads();
-    // ---- owned overlap-add over this workgroup's span ----
-    for (int p = p_lo + tid; p < p_hi; p += SY_THREADS) {
-      float acc = 0.f;
-      const int t_hi = p / a.hop;                      // the last frame that starts at or before p
-      for (int t = t_hi - a.extra; t <= t_hi; ++t) {   // ascending t: the fixed summation order
-        const int off = p - t * a.hop;
-        if (t >= 0 && t < a.width && off < a.nfft) acc += fr[(t - t0) * 2 * a.nfft + off];
-      }
-      out[p - half] = acc / a.wss[p - half];
-    }
+    overlap_add_span(a.g, s, c, tid);
   }
 }
-
-bool aligned8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 
 }  // namespace
 
@@ -371,17 +298,16 @@ extern "C" int drsa_amd_mel_relevance_to_stft(const float* relevance, const floa
   LiftArgs a{};
   const int nblk = (width + LF_TT - 1) / LF_TT;
   DRSA_REQUIRE(n_src * nblk < (1LL << 31), "mel_relevance_to_stft: too many sources");
-  int64_t off = 0;
-  auto take = [&](int64_t n) { int64_t o = off; off += (n + 3) & ~3LL; return (int)o; };
-  a.o_ax = take((int64_t)n_freq * LF_TS);
-  a.o_den = take((int64_t)n_mels * LF_TT);
-  a.o_q = take((int64_t)n_mels * LF_TT);
-  a.o_lo = take(n_freq);
-  a.o_n = take(n_freq);
-  a.o_off = take(n_freq);
-  a.o_w = take(bin_nnz);
-  const size_t smem = (size_t)off * 4;
-  if (smem > SA_LDS_MAX) {
+  LdsCarve lds;
+  a.o_ax = lds.take((int64_t)n_freq * LF_TS);
+  a.o_den = lds.take((int64_t)n_mels * LF_TT);
+  a.o_q = lds.take((int64_t)n_mels * LF_TT);
+  a.o_lo = lds.take(n_freq);
+  a.o_n = lds.take(n_freq);
+  a.o_off = lds.take(n_freq);
+  a.o_w = lds.take(bin_nnz);
+  const size_t smem = lds.bytes();
+  if (smem > DRSA_LDS_MAX) {
     drsa::set_error("mel_relevance_to_stft: LDS footprint %zu B exceeds 160 KB (n_freq %d, n_mels %d)", smem, n_freq,
                     n_mels);
     return DRSA_EUNSUPPORTED;
@@ -412,20 +338,13 @@ extern "C" int drsa_amd_mel_relevance_to_stft(const float* relevance, const floa
 extern "C" int drsa_amd_heatmap_mask_large(const float* heatmaps, int64_t n_maps, int H, int W, int group,
                                            int rank_first, int rank_rest, const float* taps, int k, float* mask,
                                            void* stream) {
-  DRSA_REQUIRE(heatmaps && taps && mask, "heatmap_mask_large: null pointer");
-  DRSA_REQUIRE(n_maps >= 0 && n_maps < (1LL << 31) && H >= 1 && W >= 1 && group >= 1,
-               "heatmap_mask_large: bad n_maps/H/W/group");
-  DRSA_REQUIRE(k >= 1 && k % 2 == 1 && k <= 63,
-               "heatmap_mask_large: blur kernel size must be odd and in [1, 63] (got %d)", k);
-  DRSA_REQUIRE(k / 2 < H && k / 2 < W, "heatmap_mask_large: reflect padding %d needs a larger map than %dx%d", k / 2,
-               H, W);
-  const int64_t n = (int64_t)H * W;
-  if (n > ML_MAX_N) {
+  if (int rc = check_mask_args("heatmap_mask_large", heatmaps, n_maps, H, W, group, rank_first, rank_rest, taps, k,
+                               mask))
+    return rc;
+  if ((int64_t)H * W > ML_MAX_N) {
     drsa::set_error("heatmap_mask_large: a %dx%d map has more than %lld elements", H, W, (long long)ML_MAX_N);
     return DRSA_EUNSUPPORTED;
   }
-  DRSA_REQUIRE(rank_first >= -1 && rank_first < n && rank_rest >= -1 && rank_rest < n,
-               "heatmap_mask_large: rank must be -1 (no threshold) or in [0, H*W)");
   if (n_maps == 0) return DRSA_OK;
   MaskLargeArgs a{heatmaps, mask, taps, H, W, k, group, rank_first, rank_rest};
   a.tiles_x = (W + ML_TILE - 1) / ML_TILE;
@@ -448,50 +367,22 @@ extern "C" int drsa_amd_stft_mask_to_audio(const float* X, const float* mask, in
                                            void* stream) {
   DRSA_REQUIRE(X && mask && window && envelope && audio, "stft_mask_to_audio: null pointer");
   StftSynArgs a{};
-  DRSA_REQUIRE(n_fft >= 8 && n_fft % 2 == 0, "stft_mask_to_audio: n_fft must be even and >= 8 (got %d)", n_fft);
-  DRSA_REQUIRE(hop >= 1, "stft_mask_to_audio: bad hop");
-  DRSA_REQUIRE(hop <= n_fft, "stft_mask_to_audio: hop %d > n_fft %d leaves gaps between frames", hop, n_fft);
-  a.n_stages = factor_radices(n_fft / 2, a.radix);
-  DRSA_REQUIRE(a.n_stages > 0, "stft_mask_to_audio: n_fft/2 = %d must factor into 2, 3, 5", n_fft / 2);
-  DRSA_REQUIRE(n_src >= 0 && C >= 1 && width >= 2, "stft_mask_to_audio: need n_src >= 0, C >= 1, width >= 2");
-  DRSA_REQUIRE(aligned8(X), "stft_mask_to_audio: X is read as (re, im) pairs and must be 8-byte aligned");
-  const int extra = (n_fft + hop - 1) / hop - 1;       // earlier frames that reach into a span
-  if (extra > SY_TF / 2) {
-    drsa::set_error("stft_mask_to_audio: n_fft/hop = %d/%d overlaps more than %d frames", n_fft, hop, SY_TF / 2 + 1);
-    return DRSA_EUNSUPPORTED;
-  }
-  const int M = n_fft / 2, nfreq = M + 1;
-  a.X = X;
+  LdsCarve lds;
+  // no mel bands and no power here: the shape rules see values that pass
+  if (int rc = synth_plan("stft_mask_to_audio", a.g, lds, X, n_src, C, n_fft, hop, /*n_mels=*/1, width, /*power=*/1,
+                          window, envelope, audio))
+    return rc;
   a.mask = mask;
-  a.window = window;
-  a.wss = envelope;
-  a.out = audio;
-  a.C = C;
-  a.nfft = n_fft;
-  a.hop = hop;
-  a.width = width;
-  a.extra = extra;
-  a.G = SY_TF - extra;
-  const int64_t outlen = (int64_t)hop * (width - 1);
-  DRSA_REQUIRE(outlen + n_fft < (1LL << 30), "stft_mask_to_audio: audio too long");
-  a.outlen = (int)outlen;
-  a.nspan = (int)((M + outlen + (int64_t)a.G * hop - 1) / ((int64_t)a.G * hop));
-  DRSA_REQUIRE(n_src * a.nspan < (1LL << 31), "stft_mask_to_audio: too many sources");
-  int64_t off = 0;
-  auto take = [&](int64_t n) { int64_t o = off; off += (n + 3) & ~3LL; return (int)o; };
-  a.o_tw = take(2 * M);
-  a.o_ptw = take(2 * (M + 1));
-  a.o_win = take(n_fft);
-  a.o_mask = take((int64_t)nfreq * SY_MS);
-  a.o_fft = take((int64_t)SY_TF * 4 * M);
-  const size_t smem = (size_t)off * 4;
-  if (smem > SA_LDS_MAX) {
+  a.o_mask = lds.take((int64_t)(n_fft / 2 + 1) * SY_MS);
+  synth_take_fft(a.g, lds);
+  const size_t smem = lds.bytes();
+  if (smem > DRSA_LDS_MAX) {
     drsa::set_error("stft_mask_to_audio: LDS footprint %zu B exceeds 160 KB (n_fft %d)", smem, n_fft);
     return DRSA_EUNSUPPORTED;
   }
   if (n_src == 0) return DRSA_OK;
   DRSA_SMEM(stft_mask_to_audio_kernel, smem);
-  hipLaunchKernelGGL(stft_mask_to_audio_kernel, dim3((unsigned)(n_src * a.nspan)), dim3(SY_THREADS), smem,
+  hipLaunchKernelGGL(stft_mask_to_audio_kernel, dim3((unsigned)(n_src * a.g.nspan)), dim3(SY_THREADS), smem,
                      (hipStream_t)stream, a);
   DRSA_LAUNCH_CHECK();
   return DRSA_OK;

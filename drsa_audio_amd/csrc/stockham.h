@@ -1,7 +1,9 @@
-// Wave-local Stockham FFT pieces shared by the log-mel front end (logmel.hip) and the audio
-// back end (audiogen.hip): complex helpers, forward radix-2/3/4/5 butterflies, one Stockham pass
-// over LDS ping-pong buffers, and the host-side radix factoring.  Forward transforms only: the
-// inverse in audiogen.hip is conj(DFT(conj z)).
+// Wave-local real FFT pieces shared by the log-mel front end (logmel.hip) and the audio back end
+// (audiogen.hip, stft_audio.hip; audio_synth.h): complex helpers, the twiddle tables, forward
+// radix-2/3/4/5 butterflies, one Stockham pass over LDS ping-pong buffers and the whole M-point
+// transform, the real-input split of the forward n_fft = 2M-point real transform, the inverse real
+// transform of one frame (half-length packing, conj(DFT(conj z)), window and 1/n_fft), reflect
+// padding, and the host-side radix factoring.  logmel800_kernel has its own tables and transform.
 #pragma once
 
 #include "common.h"
@@ -24,6 +26,27 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// twiddle tables from exact fp64 angles rounded once to fp32: tw[j] = W_M^j (j < M), ptw[k] = W_N^k
+// (k <= M, N = 2M)
+__device__ __forceinline__ void fill_twiddles(cf* tw, cf* ptw, int M, int tid, int nthreads) {
+  for (int j = tid; j < M; j += nthreads) {
+    double s, c;
+    sincospi(2.0 * (double)j / (double)M, &s, &c);
+    tw[j] = {(float)c, (float)-s};
+  }
+  for (int k = tid; k <= M; k += nthreads) {
+    double s, c;
+    sincospi((double)k / (double)M, &s, &c);
+    ptw[k] = {(float)c, (float)-s};
+  }
+}
+
+// index i of a length-n axis under reflect padding (torch pad_mode="reflect"; -n < i < 2n - 1)
+__device__ __forceinline__ int reflect_index(int i, int n) {
+  i = i < 0 ? -i : i;
+  return i >= n ? 2 * (n - 1) - i : i;
 }
 
 // forward DFT butterflies (sign -i), in place on v[0..R)
@@ -113,6 +136,44 @@ __device__ __forceinline__ cf* stockham_fft(cf* a, cf* b, const cf* tw, int M, i
     dst = t;
   }
   return src;
+}
+
+// Real-input split: bin k <= M of the 2M-point transform of the real frame x, from the M-point
+// transform Z of z[n] = x[2n] + i x[2n+1]:
+//   X[k] = E[k] + W_N^k O[k],  E = (Z_k + conj Z_{M-k})/2,  O = (Z_k - conj Z_{M-k})/(2i)
+__device__ __forceinline__ cf real_split(const cf* Z, const cf* ptw, int k, int M) {
+  const cf zk = Z[k == M ? 0 : k];
+  const cf zr = Z[k == 0 ? 0 : M - k];
+  const cf zc = {zr.x, -zr.y};
+  const cf e = cscale(cadd(zk, zc), 0.5f);
+  const cf d = csub(zk, zc);
+  const cf o = {0.5f * d.y, -0.5f * d.x};
+  return cadd(e, cmul(ptw[k], o));
+}
+
+// The inverse 2M-point real transform of one wave's frame from its bins Y(k), k <= M, windowed and
+// scaled by invN = 1/n_fft into fo[0..2M), the wave's buffer (a or b) that the passes leave free.
+// The imaginary parts of Y(0) and Y(M), a real signal's DC and Nyquist bins, are dropped (as irfft
+// does).  Half-length packing: z[n] = x[2n] + i x[2n+1] = IDFT_M(Z)/2,
+//   Z[k] = (Y[k] + conj Y[M-k]) + i (Y[k] - conj Y[M-k]) conj(W_N^k);   IDFT = conj DFT conj
+template <class Bins>
+__device__ __forceinline__ void inverse_real_frame(Bins Y, cf* a, cf* b, float* fo, const cf* tw, const cf* ptw,
+                                                   const float* win, float invN, int M, int n_stages,
+                                                   const int* radix, int lane) {
+  for (int k = lane; k < M; k += 64) {
+    cf yk = Y(k), ym = Y(M - k);
+    if (k == 0) yk.y = ym.y = 0.f;                     // the only k < M that reads bins 0 and M
+    const cf yc = {ym.x, -ym.y};
+    const cf e = cadd(yk, yc);
+    const cf o = cmul(csub(yk, yc), cf{ptw[k].x, -ptw[k].y});
+    a[k] = {e.x - o.y, -(e.y + o.x)};
+  }
+  wave_lds_sync();
+  const cf* F = stockham_fft(a, b, tw, M, n_stages, radix, lane);
+  for (int n = lane; n < M; n += 64) {
+    fo[2 * n] = (F[n].x * invN) * win[2 * n];
+    fo[2 * n + 1] = (-F[n].y * invN) * win[2 * n + 1];
+  }
 }
 
 // M = 2^a 3^b 5^c -> its radices (4s first), or -1

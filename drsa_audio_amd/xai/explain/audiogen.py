@@ -312,17 +312,19 @@ class Mel2Audio:
             self._require_model_shape(H, W)
             mel, X = self.analyse_stft(wavs)
             maps = self.lift_to_stft(torch.cat([std, sub], dim=1), mel, X)
-            n = maps.size(-2) * maps.size(-1)
-            masks = heatmap_masks(maps, self.smoother, percentile_rank(50, n),
-                                  percentile_rank(percentile, n) if percentile else -1, group=K + 1)
-            return self.normalise(self.stft_masks_to_audio(X, masks), wavs)
+            return self.normalise(self.stft_masks_to_audio(X, self._batch_masks(maps, percentile)), wavs)
         mel, X = self._analyse(wavs, peak_norm=True)
         if (H, W) != tuple(mel.shape[1:]):
             raise ValueError(f"heatmaps are {H}x{W} but the mel is {mel.size(1)}x{mel.size(2)}")
-        n = H * W
-        masks = heatmap_masks(torch.cat([std, sub], dim=1), self.smoother, percentile_rank(50, n),
-                              percentile_rank(percentile, n) if percentile else -1, group=K + 1)
+        masks = self._batch_masks(torch.cat([std, sub], dim=1), percentile)
         return self.normalise(self._synthesise(mel, X, masks), wavs)
+
+    def _batch_masks(self, maps: torch.Tensor, percentile) -> torch.Tensor:
+        """The masks of maps [B, K+1, H, W]: a source's first map (its standard heatmap) is cut at
+        percentile 50, the others at ``percentile`` (not cut when it is falsy)."""
+        n = maps.size(-2) * maps.size(-1)
+        return heatmap_masks(maps, self.smoother, percentile_rank(50, n),
+                             percentile_rank(percentile, n) if percentile else -1, group=maps.size(1))
 
     def make_audios(self, sample_info: Dict[str, Union[np.ndarray, torch.Tensor]], original_audio=None,
                     startpoint=None, num_concepts: int = 4, percentile=50, path_to_sample: Optional[str] = None,

@@ -129,8 +129,9 @@ def test_istft_envelope_host_table_and_refusal():
 
 
 # ------------------------------------------------------- argument rejections
-_BUF = (ctypes.c_float * 4)()
+_BUF = (ctypes.c_double * 4)()                                           # 8-byte aligned
 _P = ctypes.cast(_BUF, ctypes.c_void_p)
+_ODD = ctypes.c_void_p(_P.value + 4)
 _VALID = {
     "stft_mel_phase": dict(wav=_P, n_chunks=1, chunk_stride=16000, chunk_len=16000, n_fft=480, hop=240, n_mels=64,
                            width=64, frame0=0, power=1, window=_P, band_lo=_P, band_n=_P, band_off=_P, band_w=_P,
@@ -170,6 +171,9 @@ _REJECTIONS = [
     ("mel_to_audio", dict(width=1), _EINVAL, "width"),
     ("audio_normalize", dict(audio=None), _EINVAL, "null"),
     ("audio_normalize", dict(wav=_P, wav_len=0), _EINVAL, "wav_len"),
+    # new rows go last: a row's place in the table is part of its test id
+    ("stft_mel_phase", dict(X=_ODD), _EINVAL, "aligned"),                   # X is written as float2
+    ("mel_to_audio", dict(X=_ODD), _EINVAL, "aligned"),                     # X is read as float2
 ]
 
 

@@ -248,6 +248,36 @@ def test_synthesis_refuses_what_does_not_fit_the_lds():
         m.stft_masks_to_audio(X, torch.ones(1, 1, 481, 9, device=DEV))
 
 
+@pytest.mark.parametrize("n_fft,hop,width", [(16, 4, 30), (8, 4, 40)])
+def test_the_two_synthesis_entries_agree_bit_for_bit(n_fft, hop, width):
+    """drsa_amd_mel_to_audio and drsa_amd_stft_mask_to_audio where their fronts give the same
+    floats: n_mels = n_freq, P = identity, mel = 1, power 1, and a spectrum of unit phasors
+    {1, -1, i, -i}.  Then |X| = 1 and 1/sqrtf(1) = 1, the contraction returns the mask itself, and
+    mag x phase and mask x X are the same products; everything after is the shared back half.
+    (16, 4, 30): two passes, extra 3, three spans, the first with t0 < 0 and a partial last one;
+    (8, 4, 40): one pass (the other parity of the frame buffer), extra 1, three spans."""
+    from drsa_audio_amd import _capi
+    B, C, n_freq = 2, 2, n_fft // 2 + 1
+    extra = -(-n_fft // hop) - 1
+    assert extra == {16: 3, 8: 1}[n_fft] and -(-(n_fft // 2 + hop * (width - 1)) // ((16 - extra) * hop)) == 3
+    rng = np.random.default_rng(n_fft)
+    units = np.array([[1, 0], [-1, 0], [0, 1], [0, -1]], dtype=np.float32)
+    X = _dev(units[rng.integers(0, 4, (B, width, n_freq))])                 # [B, width, n_freq, (re, im)]
+    masks = _dev(rng.uniform(0.25, 1, (B, C, n_freq, width)).astype(np.float32))
+    win = torch.hann_window(n_fft)
+    env = torch.empty(hop * (width - 1))
+    assert _capi.lib().drsa_amd_istft_envelope(win.data_ptr(), n_fft, hop, width, env.data_ptr()) == 0
+    win, env = win.to(DEV), env.to(DEV)
+    mel, eye = torch.ones(B, n_freq, width, device=DEV), torch.eye(n_freq, device=DEV)
+    a_mel, a_stft = (torch.full((B, C, hop * (width - 1)), float("nan"), device=DEV) for _ in range(2))
+    _capi.call("drsa_amd_mel_to_audio", mel.data_ptr(), X.data_ptr(), masks.data_ptr(), B, C, n_fft, hop, n_freq,
+               width, 1, win.data_ptr(), eye.data_ptr(), env.data_ptr(), a_mel.data_ptr(), _capi.stream_ptr(DEV))
+    _capi.call("drsa_amd_stft_mask_to_audio", X.data_ptr(), masks.data_ptr(), B, C, n_fft, hop, width,
+               win.data_ptr(), env.data_ptr(), a_stft.data_ptr(), _capi.stream_ptr(DEV))
+    assert torch.isfinite(a_stft).all() and float(a_stft.abs().max()) > 0
+    assert torch.equal(a_mel.view(torch.int32), a_stft.view(torch.int32))
+
+
 # ------------------------------------------------------------------ end to end
 @pytest.mark.parametrize("case,B,K", [("toy", 3, 2), ("gtzan", 2, 2)])
 def test_make_audios_batch_is_its_four_stages(case, B, K):
