@@ -132,6 +132,8 @@ SIGNATURES = {
                                               _f32, _fp, _vp]),
     "drsa_amd_heatmap_mask_large": (_i32, [_fp, _i64, _i32, _i32, _i32, _i32, _i32, _fp, _i32, _fp, _vp]),
     "drsa_amd_stft_mask_to_audio": (_i32, [_fp, _fp, _i64, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _vp]),
+    "drsa_amd_track_stitch_workspace_bytes": (_sz, [_i32, _i32, _i64]),
+    "drsa_amd_track_stitch": (_i32, [_fp, _fp, _ip, _fp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _vp, _sz, _vp]),
 }
 
 class DrsaProblem(C.Structure):

@@ -726,6 +726,38 @@ int drsa_amd_heatmap_mask_large(const float* heatmaps, int64_t n_maps, int H, in
 int drsa_amd_stft_mask_to_audio(const float* X, const float* mask, int64_t n_src, int C, int n_fft, int hop,
                                 int width, const float* window, const float* envelope, float* audio, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Whole-track explanations: overlapping chunks' maps stitched into one track-length map per
+ * concept (xai/explain/track.py, DESIGN.md "Whole-track explanations").  csrc/track_stitch.hip.
+ * ------------------------------------------------------------------------- */
+
+/* n chunks of width W, chunk c starting at track column c*h (1 <= h <= W), Wt = (n-1)*h + W:
+ *   std_maps [n, 1, H, W]   standard maps; NULL: C = K output maps and no map 0
+ *   sub      [n, K, H, W]   concept maps in each chunk's own slot order
+ *   order    [n, K] int64   order[c][j] = the concept in slot j of chunk c (HeatmapGenerator's "mask");
+ *                           NULL = identity
+ *   taper    [W]            weights, strictly positive (a precondition: they are device data)
+ *   out      [C, H, Wt]     C = K + 1 (K when std_maps = NULL): map 0 the standard map, map k concept k - 1
+ *   act      [C, Wt]        act[k][u] = sum over the rows r of out[k][r][u]
+ * Column u is covered by the chunks c = max(0, ceil((u - W + 1) / h)) .. min(n - 1, u / h), with
+ * t = u - c*h.  Over them, c ascending:
+ *   num = one fmaf(taper[t], x_c[r][t], num) chain from +0;  den = the plain sum of taper[t];
+ *   out[k][r][u] = num / den (IEEE division).
+ * act: rows go in blocks of 32; in a block, the 8 sums over the rows r = j (mod 8), r ascending, each
+ * from +0, are added j ascending from +0; the blocks' sums are added block ascending from +0.
+ * No atomics: out and act are bit-identical from run to run.
+ * order on the device is not read on the host: the caller guarantees that every row is a permutation
+ * of 0..K-1 (a slot that names no concept of 0..K-1 is ignored; a concept no slot names reads slot 0).
+ * An order in host memory is checked here (DRSA_EINVAL), and refused when it is pageable memory
+ * that the device cannot read.  16-byte accesses when W, h are multiples of 4 and every pointer is
+ * 16-byte aligned, 4-byte accesses otherwise; the results do not depend on which.
+ * ws: drsa_amd_track_stitch_workspace_bytes(C, H, Wt) bytes (0 when H <= 32): the row blocks' partial
+ * act sums.  There is no empty problem: n, K, H >= 1 are required. */
+size_t drsa_amd_track_stitch_workspace_bytes(int C, int H, int64_t Wt);
+int drsa_amd_track_stitch(const float* std_maps, const float* sub, const int64_t* order, const float* taper, int n,
+                          int K, int H, int W, int h, float* out, float* act, void* ws, size_t ws_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
